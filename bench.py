@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- vocoder-inference throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment launches its own N ranks (it re-executes
@@ -11,8 +11,13 @@ A "step" is one forward of the hot path (HiFi-GAN V1 generator, mel -> waveform)
 synthetic mels already resident in HBM: BASELINE.json configs[1] = B=64 x 80 mel x 256 frames per GPU
 (weak scaling: every rank runs its own B=64 shard; for N>1 the step includes the RCCL gather of the
 audio to rank 0; before the timed region rank 0 checks that the gathered [64 N, L] tensor equals N
-single-GPU runs bit for bit).  Prints ONE JSON line on rank 0; at N = 1 the line also carries the CPU baseline, the
-PyTorch-ROCm library baseline and the other BASELINE.json configs (C3 BigVGAN, C5 VITS, mel front end, latency).
+single-GPU runs bit for bit, with --full).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figure, ms_per_step, and the roofline of the
+dominant kernel read from HIP events of the timed steps themselves).  --dump-outputs DIR writes the audio of the last timed step
+(what a caller of the path receives) as DIR/wav.npy, float32.  --full adds everything else: for N > 1 the bitwise gather check and
+the per-rank diagnostics; at N = 1 the CPU baseline, the PyTorch-ROCm library baseline, the exact-fp32 mode and the other
+BASELINE.json configs (C3 BigVGAN, C5 VITS, mel front end, latency), and the full record in a side file.
 """
 import argparse
 import json
@@ -450,6 +455,24 @@ def multi_gpu_diagnostics(model, mel, total_items, device, per_rank_ms, reps=5):
                            "when issued asynchronously behind the next batch's forward (step - compute_only); gather_ms_pcm16: int16 rows"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, wav):
+    """The audio the timed path returned in its last step ([B, 1, L] float32; N > 1: the gathered [B N, L] on rank 0) as
+    DIR/wav.npy.  Above 64 MB a fixed, seeded sample of rows is written instead, with their indices in DIR/wav_rows.npy."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    a = wav.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - (1 << 20)) // a[0].nbytes        # 1 MB left for the index file
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        a = a[rows]
+        np.save(os.path.join(dirname, "wav_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "wav.npy"), np.ascontiguousarray(a))
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -469,10 +492,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU, library and other-config legs (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU, library and other-config legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (CPU / library baselines, exact fp32, other configs; N > 1: gather check and diagnostics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio of the last timed step to DIR/wav.npy (float32, at most 64 MB: a seeded sample of rows beyond)")
     ap.add_argument("--precision", choices=sorted(PRECISIONS), default="f16x3",
                     help="arithmetic of the conv contractions (include/amphion_hip.h: amp_precision)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -530,7 +559,7 @@ def main():
         step()
     fence()
     gather_check = None
-    if world > 1:
+    if world > 1 and args.full:
         # the gathered [64 N, L] tensor must equal N single-GPU runs bit for bit: rank 0 recomputes
         # every rank's shard (same seeded mel, same weights) on its own GPU and compares -- untimed
         got = step()
@@ -571,7 +600,9 @@ def main():
     # (amp_gen_kernel_name: the launch policy's actual pick for this shape, rocprofv3 spelling), not assumed here
     knames = sorted({n for back in range(args.steps) for n in model.kernel_names(100 + 16 * DOM_STAGE + DOM_RB, back)})
     model.set_profiling(0)
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if world > 1 and args.full:
         # after the timed region and after its event ring has been read (the diagnostics run forwards of their own); collective calls,
         # so every rank makes them -- and a failure is reported in the line, it does not cost the line
         try:
@@ -674,7 +705,7 @@ def main():
             result["gather_check"] = gather_check
         if multi:
             result.update(multi)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             del out
             # the side legs must never cost the headline line: a failure is reported in place of the figure
             legs = [("other_configs", other_configs), ("library_baseline", lambda: library_baseline(sd, hp, device)),
@@ -714,12 +745,15 @@ def main():
         # `roofline`, `cpu_baseline`, one figure per leg, <= 6 KB, with the summary repeated as the LAST key -- a record that keeps only the head or
         # only the last ~2 KB of the line still carries every BASELINE config's number.
         detail_path = os.path.join(ROOT, "gpurun_out", "bench_detail.json" if "other_configs" in result else "bench_detail_headline_only.json")
-        try:
-            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-            with open(detail_path, "w") as f:
-                json.dump(result, f)
-        except OSError:
-            detail_path = None
+        if args.full:
+            try:
+                os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+                with open(detail_path, "w") as f:
+                    json.dump(result, f)
+            except OSError:
+                detail_path = None
+        else:
+            detail_path = None      # a plain run writes no side file
         line = compact_line(result, detail_path)
         print(json.dumps(line))
     if world > 1:

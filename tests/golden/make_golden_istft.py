@@ -25,10 +25,14 @@ def main():
         phase = (torch.rand(B, nfft // 2 + 1, F, generator=g) * 2 - 1) * np.pi
         with torch.no_grad():
             wav = st.inverse(mag, phase)
+            # the same inverse in float64: the oracle's restatement is pinned on it, free of the fp32 accumulation order of the host's
+            # conv kernels (which differs between CPU models by a few ulp)
+            wav64 = st.double().inverse(mag.double(), phase.double())
         out[f"{tag}_cfg"] = np.array([nfft, hop, win])
         out[f"{tag}_mag"] = mag.numpy()
         out[f"{tag}_phase"] = phase.numpy()
         out[f"{tag}_wav"] = wav.numpy()
+        out[f"{tag}_wav64"] = wav64.numpy()
         out[f"{tag}_wss"] = stft_mod.window_sumsquare("hann", F, hop_length=hop, win_length=win, n_fft=nfft, dtype=np.float32)
     np.savez_compressed(os.path.join(HERE, "golden_istft.npz"), **out)
     for k, v in out.items():

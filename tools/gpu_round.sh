@@ -2,7 +2,7 @@
 # One GPU-box visit, assembled from named steps (round 3: replaces the 47 single-use visit scripts of round 2).
 #   usage (repo root on the GPU box):  bash tools/gpu_round.sh <tag> [step ...]        default steps: tests bench prof pmc smoke
 #   steps   tests     pytest -m gpu -x -q (what the driver runs at round end); PYTEST_N=<n> adds xdist workers
-#           bench     the full bench.py line (CPU / library baselines, other configs)            -> bench.json
+#           bench     bench.py --full (CPU / library baselines, other configs)                    -> bench.json
 #           prof      rocprofv3 --kernel-trace --stats over bench.py --no-cpu-baseline           -> prof/kt_kernel_stats.csv, manifest.tsv, roofline_table.txt
 #           pmc       FETCH_SIZE and WRITE_SIZE passes (separate runs, kernel-trace only)         -> pmc_fetch/, pmc_write/
 #           sq        four SQ counter passes over ONE config-2 forward (or $SQCMD)                -> sq_table.csv, sq_summary.txt
@@ -30,7 +30,7 @@ for STEP in $STEPS; do
       NW=${PYTEST_N:-0}; if [ "$NW" != "0" ]; then XD="-n $NW"; else XD=""; fi
       ( timeout 1500 python -m pytest tests -m gpu -x -q $XD 2>&1 | tail -40 ) > $OUT/pytest_gpu.txt; tail -5 $OUT/pytest_gpu.txt ;;
     bench)
-      ( timeout 600 python bench.py --steps 10 --warmup 3 2> $OUT/bench.err | tail -1 ) > $OUT/bench.json; cut -c1-1500 $OUT/bench.json ;;
+      ( timeout 600 python bench.py --steps 10 --warmup 3 --full 2> $OUT/bench.err | tail -1 ) > $OUT/bench.json; cut -c1-1500 $OUT/bench.json ;;
     prof)
       rm -f $REPO/$OUT/manifest.tsv     # the library's launch manifest of the same run (amp_internal.h), joined by tools/roofline_table.py
       ( cd /tmp && AMP_LAUNCH_MANIFEST=$REPO/$OUT/manifest.tsv timeout 600 $PROF --stats -d $REPO/$OUT/prof -o kt -- $PROFCMD > $REPO/$OUT/prof_bench.json 2> $REPO/$OUT/prof.err )
