@@ -84,7 +84,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     units = _units()
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         objs = list(ex.map(_compile, units))
-    cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + [os.path.join(OBJ, o) for o in objs]
+    # --no-undefined: a tap count generator.hip dispatches to but the lists above do not build fails here, not at dlopen
+    cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--no-undefined", "-o", LIB] + [os.path.join(OBJ, o) for o in objs]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed: " + " ".join(cmd) + "\n" + r.stdout + r.stderr)

@@ -173,25 +173,29 @@ struct ConvPlan {
 // Chooses the kernel variant for a conv with `ntaps` taps, GEMM rows M, halo_total columns and Tq
 // columns per item.  Returns false if unsupported.
 bool choose_plan(int ntaps, int M, int halo_total, int Tq, ConvPlan* plan);
-hipError_t launch_conv(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);        // exact f32 MFMA
-hipError_t launch_conv_f16x3(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);  // split-f16 MFMA
+
+// ---- per-tap-count kernels: each TU below is compiled once per tap count (-DAMP_KT=k, the lists in build.py) and instantiates these
+// templates for KT = AMP_KT only; generator.hip maps a runtime tap count onto them
+template <int KT> hipError_t launch_conv(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);        // exact f32 MFMA (conv_mfma.hip)
+template <int KT> hipError_t launch_conv_f16x3(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);  // split-f16 MFMA (conv_f16x3.hip)
+// row-blocked conv (conv_blk_f16x3.hip): tile width for cm chunks per staging round and a halo, 0 = not covered; launch
+template <int KT> int conv_blk_nt(int cm, int halo_total);
+template <int KT> hipError_t launch_conv_blk(int cm, int wn, const ConvArgs& a, hipStream_t stream);
 // frame-rate convs (conv_small_f16x3.hip): whole-K staging; epi 0 standard, 1 gate, 2 WN accumulate; ni 2 | 4
 constexpr int kSmallConvMaxChunks = 16;
-hipError_t launch_conv_small(int KT, int ni, int epi, const ConvArgs& a, hipStream_t stream);
-// fused pair: output columns per workgroup for (C, k, dilation), 0 = not covered; launch
-int pair_tile(int k, int C, int dil);
-hipError_t launch_pair(int k, const PairArgs& a, hipStream_t stream);
-// strip-mined fused pair (pair_strip_f16x3.hip): columns per step for (C, k, dilation), 0 = not covered
-int strip_step(int k, int C, int dil, int wide, int* wg_per_cu);
-hipError_t launch_strip(int k, const PairArgs& a, hipStream_t stream);
-
-// whole ResBlock1 (rb_f16x3.hip): tile width for (C, k, max dilation) in form `wide`, 0 = not covered; launch
-int rb_tile(int k, int C, int max_dil, int wide);
-hipError_t launch_rb(int k, const RbArgs& a, int wide, hipStream_t stream);
-
-// whole AMPBlock1 (ampb_f16x3.hip): tile width for (C, k, max dilation) in form `wide`, 0 = not covered; launch
-int ampb_tile(int k, int C, int max_dil, int wide);
-hipError_t launch_ampb(int k, const AmpbArgs& a, int wide, hipStream_t stream);
+template <int KT> hipError_t launch_conv_small(int ni, int epi, const ConvArgs& a, hipStream_t stream);
+// fused pair (pair_f16x3.hip): output columns per workgroup for (C, dilation), 0 = not covered; launch
+template <int KT> int pair_tile(int C, int dil);
+template <int KT> hipError_t launch_pair(const PairArgs& a, hipStream_t stream);
+// strip-mined fused pair (pair_strip_f16x3.hip): columns per step for (C, dilation), 0 = not covered
+template <int KT> int strip_step(int C, int dil, int wide, int* wg_per_cu);
+template <int KT> hipError_t launch_strip(const PairArgs& a, hipStream_t stream);
+// whole ResBlock1 (rb_f16x3.hip): tile width for (C, max dilation) in form `wide`, 0 = not covered; launch
+template <int KT> int rb_tile(int C, int max_dil, int wide);
+template <int KT> hipError_t launch_rb(const RbArgs& a, int wide, hipStream_t stream);
+// whole AMPBlock1 (ampb_f16x3.hip): tile width for (C, max dilation) in form `wide`, 0 = not covered; launch
+template <int KT> int ampb_tile(int C, int max_dil, int wide);
+template <int KT> hipError_t launch_ampb(const AmpbArgs& a, int wide, hipStream_t stream);
 
 // conv_post: y[b,0,t] = tanh( bias + sum_i sum_j w[i][j] * act_in(x[b,i,t+j-pad]) )   (Cout == 1)
 hipError_t launch_conv_post(const float* x, const float* w_dev /*[Cin*K]*/, const float* bias_dev /*[1] or null*/,
@@ -268,14 +272,14 @@ inline hipError_t ensure_dynamic_lds(size_t bytes) {
 // Which kernels a stretch of launch_* calls issued, as rocprofv3 prints them ("pair_strip_kernel<11, 2, 2, 4, 320, 2, 4, 1>"):
 // while the calling thread points tl_kernel_log at a string (a profiled amp_gen_forward does, per resblock), every launch
 // appends its kernel's name once (" | "-joined) -- bench.py reports the variant the policy actually picked, not a literal.
-extern thread_local std::string* tl_kernel_log;
+extern __thread std::string* tl_kernel_log;   // (__thread: constant-initialised, no TLS init function for other TUs to import)
 // AMP_LAUNCH_MANIFEST=<file> (read once per process): every launch appends one line
 //     <kernel name with its template arguments>\t<workgroups>\t<algorithmic GFLOP>\t<algorithmic MB>\t<what it computes>
 // -- the launcher's OWN statement of the work a launch does, which tools/roofline_table.py joins with rocprofv3's per-dispatch durations
 // by (name, workgroups) instead of guessing shapes from template arguments.  Off: one predictable branch per launch.
 bool manifest_on();
 void manifest_add(const char* name, unsigned long long workgroups, double gflop, double mb, const char* what);
-extern thread_local char tl_last_kernel[160];
+extern __thread char tl_last_kernel[160];
 template <typename... A>
 inline void note_kernel(const char* base, A... args) {
     if (!tl_kernel_log && !manifest_on()) return;

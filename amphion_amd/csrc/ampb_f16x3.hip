@@ -524,13 +524,10 @@ static hipError_t launch_ampb_one(const AmpbArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // Tile width W (columns evaluated per workgroup; outputs per tile = W - 2 * rh) for C channels in form `wide`
 // (1: eight waves, one workgroup per CU; 0: four waves, two per CU), or 0 when not covered.
-int AMP_CAT(ampb_tile_kt, AMP_KT)(int C, int max_dil, int wide) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+int ampb_tile(int C, int max_dil, int wide) {
     const int reach = (KT - 1) / 2 * max_dil;
     if (reach > 32) return 0;
     if (C == 32) return wide ? 1024 : 512;
@@ -538,12 +535,15 @@ int AMP_CAT(ampb_tile_kt, AMP_KT)(int C, int max_dil, int wide) {
     return 0;
 }
 
-hipError_t AMP_CAT(launch_ampb_kt, AMP_KT)(const AmpbArgs& a, int wide, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_ampb(const AmpbArgs& a, int wide, hipStream_t stream) {
     constexpr int RING = KT >= 7 ? 4 : (KT == 5 ? 3 : 0);   // (k = 5: a ring of three taps instead of five resident ones leaves every form without spills)
     if (a.C == 32) return wide ? launch_ampb_one<KT, 1, 8, RING, 32>(a, stream) : launch_ampb_one<KT, 1, 4, RING, 32>(a, stream);
     if (a.C == 64 && wide) return launch_ampb_one<KT, 2, 4, RING, 32>(a, stream);
     return hipErrorInvalidValue;
 }
+
+template int ampb_tile<AMP_KT>(int, int, int);
+template hipError_t launch_ampb<AMP_KT>(const AmpbArgs&, int, hipStream_t);
 
 }  // namespace amp

@@ -389,9 +389,6 @@ static hipError_t launch_blk_one(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // Tile width (columns) of the blocked kernel for this tap count, chunks per round and staged halo, 0 = not covered.
 //   KT = 2 (transposed convs, 1 halo column): 96-column tiles -- Tq = T + 1 columns cut into 128s leaves the first
 //   up-sampling layer (T = 256) a third tile with ONE column; one or two chunks per round (180 / 227 VGPRs);
@@ -402,16 +399,16 @@ static hipError_t launch_blk_one(const ConvArgs& a, hipStream_t stream) {
 #ifndef AMP_BLK_RING
 #define AMP_BLK_RING 4
 #endif
-int AMP_CAT(conv_blk_nt_kt, AMP_KT)(int cm, int halo_total) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+int conv_blk_nt(int cm, int halo_total) {
     if (KT == 2) return ((cm == 1 || cm == 2) && halo_total <= 32) ? 96 : 0;
     return (cm == 1 && halo_total <= 64) ? 128 : 0;
 }
 
 // cm = chunks per staging round, wn = waves along the columns (1 | 2: 256- | 128-row groups); the caller guarantees
 // M % (256 / wn) == 0, nchunks % cm == 0, tanh_out == 0 and tiles of wn * conv_blk_nt_kt*(cm, halo) columns
-hipError_t AMP_CAT(launch_conv_blk_kt, AMP_KT)(int cm, int wn, const ConvArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_conv_blk(int cm, int wn, const ConvArgs& a, hipStream_t stream) {
     if constexpr (KT == 2) {
         if (wn != 1) return hipErrorInvalidValue;
         if (cm == 2) return launch_blk_one<KT, 3, 32, 2>(a, stream);
@@ -430,5 +427,8 @@ hipError_t AMP_CAT(launch_conv_blk_kt, AMP_KT)(int cm, int wn, const ConvArgs& a
         return launch_blk_one<KT, 4, 64, 1, AMP_BLK_RING>(a, stream);
     }
 }
+
+template int conv_blk_nt<AMP_KT>(int, int);
+template hipError_t launch_conv_blk<AMP_KT>(int, int, const ConvArgs&, hipStream_t);
 
 }  // namespace amp

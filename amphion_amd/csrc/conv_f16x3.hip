@@ -390,11 +390,8 @@ static hipError_t launch_one_h(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
-hipError_t AMP_CAT(launch_conv_h_kt, AMP_KT)(const ConvPlan& p, const ConvArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_conv_f16x3(const ConvPlan& p, const ConvArgs& a, hipStream_t stream) {
     // 4 accumulator tiles (64 VGPRs) per wave: the register budget goes to the per-chunk A-fragment set
     // (8 * KT VGPRs) instead, see the kernel.  NI = 2 halves the tile width for grids that would leave most of
     // the 256 CUs idle (single utterances, frame-rate convs): twice the workgroups, half the work in each.
@@ -412,5 +409,7 @@ hipError_t AMP_CAT(launch_conv_h_kt, AMP_KT)(const ConvPlan& p, const ConvArgs& 
     AMP_LAUNCH_NI(4)
 #undef AMP_LAUNCH_NI
 }
+
+template hipError_t launch_conv_f16x3<AMP_KT>(const ConvPlan&, const ConvArgs&, hipStream_t);
 
 }  // namespace amp

@@ -257,11 +257,8 @@ static hipError_t launch_one(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
-hipError_t AMP_CAT(launch_conv_kt, AMP_KT)(const ConvPlan& p, const ConvArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_conv(const ConvPlan& p, const ConvArgs& a, hipStream_t stream) {
     if (p.HALO == 64) {
         if (p.WM == 4) return launch_one<KT, 4, 1, 8, 64>(a, stream);
         if (p.WM == 2) return launch_one<KT, 2, 2, 8, 64>(a, stream);
@@ -272,5 +269,7 @@ hipError_t AMP_CAT(launch_conv_kt, AMP_KT)(const ConvPlan& p, const ConvArgs& a,
         return launch_one<KT, 1, 4, 4, 128>(a, stream);
     }
 }
+
+template hipError_t launch_conv<AMP_KT>(const ConvPlan&, const ConvArgs&, hipStream_t);
 
 }  // namespace amp

@@ -57,13 +57,10 @@ static hipError_t launch_small_one(const ConvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // epi: 0 standard, 1 gate, 2 WN accumulate; ni: 1 (128 x 32 tiles, halo <= 32) or 2 (128 x 64 tiles, halo <= 64).
 // The caller sets a.tiles_per_item / a.wd for the tile width it asks for.
-hipError_t AMP_CAT(launch_conv_small_kt, AMP_KT)(int ni, int epi, const ConvArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_conv_small(int ni, int epi, const ConvArgs& a, hipStream_t stream) {
     if (ni == 1) {
         if (epi == 0) return launch_small_one<KT, 1, 32, 0>(a, stream);
         if (epi == 1) return launch_small_one<KT, 1, 32, 1>(a, stream);
@@ -73,5 +70,7 @@ hipError_t AMP_CAT(launch_conv_small_kt, AMP_KT)(int ni, int epi, const ConvArgs
     if (epi == 1) return launch_small_one<KT, 2, 64, 1>(a, stream);
     return launch_small_one<KT, 2, 64, 2>(a, stream);
 }
+
+template hipError_t launch_conv_small<AMP_KT>(int, int, const ConvArgs&, hipStream_t);
 
 }  // namespace amp

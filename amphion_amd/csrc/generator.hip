@@ -10,6 +10,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "amp_internal.h"
@@ -38,23 +39,59 @@ void set_error(const char* fmt, ...) {
     } while (0)
 
 // ------------------------------------------------------------------------------------------------
-// conv kernel dispatch
+// per-tap-count kernel dispatch
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_conv_kt1(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_kt2(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_kt3(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_kt5(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_kt7(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_kt11(const ConvPlan&, const ConvArgs&, hipStream_t);
+// The tap counts each per-tap-count kernel family is compiled for: CONV_TAPS, BLK_TAPS, SMALL_TAPS, PAIR_TAPS, RB_TAPS and AMPB_TAPS in
+// build.py (a count listed here but not built there is an undefined symbol when the library links).
+template <int... K> struct Taps { static constexpr int list[] = {K...}; };
+using ConvTaps = Taps<1, 2, 3, 5, 7, 11>;   // conv_mfma.hip, conv_f16x3.hip
+using BlkTaps = Taps<2, 3, 7, 11>;          // conv_blk_f16x3.hip
+using SmallTaps = Taps<1, 3, 5, 7, 11>;     // conv_small_f16x3.hip
+using PairTaps = Taps<3, 5, 7, 11>;         // pair_f16x3.hip, pair_strip_f16x3.hip
+using RbTaps = Taps<3, 5, 7, 11>;           // rb_f16x3.hip
+using AmpbTaps = Taps<3, 5, 7, 11>;         // ampb_f16x3.hip
 
-hipError_t launch_conv_h_kt1(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_h_kt2(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_h_kt3(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_h_kt5(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_h_kt7(const ConvPlan&, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_h_kt11(const ConvPlan&, const ConvArgs&, hipStream_t);
+// f(std::integral_constant<int, K>{}) for the K of the list that equals the runtime tap count k; `dflt` when k is not in the list
+template <int... K, typename R, typename F>
+static R with_taps(Taps<K...>, int k, R dflt, F&& f) {
+    R r = dflt;
+    (void)((k == K && (r = f(std::integral_constant<int, K>{}), true)) || ...);
+    return r;
+}
 
-static const int kSupportedKT[] = {1, 2, 3, 5, 7, 11};
+static hipError_t launch_conv(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    return with_taps(ConvTaps{}, p.KT, hipErrorInvalidValue, [&](auto K) { return launch_conv<K>(p, a, s); });
+}
+static hipError_t launch_conv_f16x3(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    return with_taps(ConvTaps{}, p.KT, hipErrorInvalidValue, [&](auto K) { return launch_conv_f16x3<K>(p, a, s); });
+}
+static int conv_blk_nt(int k, int cm, int halo) { return with_taps(BlkTaps{}, k, 0, [&](auto K) { return conv_blk_nt<K>(cm, halo); }); }
+static hipError_t launch_conv_blk(int k, int cm, int wn, const ConvArgs& a, hipStream_t s) {
+    return with_taps(BlkTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_conv_blk<K>(cm, wn, a, s); });
+}
+static hipError_t launch_conv_small(int k, int ni, int epi, const ConvArgs& a, hipStream_t s) {
+    return with_taps(SmallTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_conv_small<K>(ni, epi, a, s); });
+}
+static int pair_tile(int k, int C, int dil) { return with_taps(PairTaps{}, k, 0, [&](auto K) { return pair_tile<K>(C, dil); }); }
+static hipError_t launch_pair(int k, const PairArgs& a, hipStream_t s) {
+    return with_taps(PairTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_pair<K>(a, s); });
+}
+static int strip_step(int k, int C, int dil, int wide, int* wg) {
+    return with_taps(PairTaps{}, k, 0, [&](auto K) { return strip_step<K>(C, dil, wide, wg); });
+}
+static hipError_t launch_strip(int k, const PairArgs& a, hipStream_t s) {
+    return with_taps(PairTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_strip<K>(a, s); });
+}
+static int rb_tile(int k, int C, int max_dil, int wide) { return with_taps(RbTaps{}, k, 0, [&](auto K) { return rb_tile<K>(C, max_dil, wide); }); }
+static hipError_t launch_rb(int k, const RbArgs& a, int wide, hipStream_t s) {
+    return with_taps(RbTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_rb<K>(a, wide, s); });
+}
+static int ampb_tile(int k, int C, int max_dil, int wide) {
+    return with_taps(AmpbTaps{}, k, 0, [&](auto K) { return ampb_tile<K>(C, max_dil, wide); });
+}
+static hipError_t launch_ampb(int k, const AmpbArgs& a, int wide, hipStream_t s) {
+    return with_taps(AmpbTaps{}, k, hipErrorInvalidValue, [&](auto K) { return launch_ampb<K>(a, wide, s); });
+}
 
 // ---- f16 operand-range guard -------------------------------------------------------------------------------------
 // The f16x3 kernels OR 1 into a per-device word when a staged operand does not fit the split-f16 form (|x| > 4094
@@ -70,8 +107,8 @@ struct RangeGuard {
     bool pending = false;          // an async copy of `dev` is in flight / unread
 };
 static RangeGuard g_guard[64];                    // op-level launches (amp_conv_forward, amp_pair_forward, ...): one word per device
-thread_local std::string* tl_kernel_log = nullptr;    // amp_internal.h: note_kernel()
-thread_local char tl_last_kernel[160] = "";
+__thread std::string* tl_kernel_log = nullptr;    // amp_internal.h: note_kernel()
+__thread char tl_last_kernel[160] = "";
 // launch manifest (amp_internal.h): AMP_LAUNCH_MANIFEST=<file>, read once; lines are appended and flushed per launch (profiling runs only)
 static FILE* manifest_file() {
     static FILE* f = [] {
@@ -187,14 +224,14 @@ static int default_precision() {
 }
 
 static int round_up_taps(int ntaps) {
-    for (int kt : kSupportedKT)
+    for (int kt : ConvTaps::list)
         if (kt >= ntaps) return kt;
     return -1;
 }
 
 bool choose_plan(int KT, int M, int halo_total, int /*Tq*/, ConvPlan* plan) {
     bool ok = false;
-    for (int kt : kSupportedKT) ok |= (kt == KT);
+    for (int kt : ConvTaps::list) ok |= (kt == KT);
     if (!ok || halo_total > 128) return false;
     plan->KT = KT;
     plan->HALO = halo_total <= 64 ? 64 : 128;
@@ -202,134 +239,6 @@ bool choose_plan(int KT, int M, int halo_total, int /*Tq*/, ConvPlan* plan) {
     else if (M > 32) { plan->WM = 2; plan->WN = 2; plan->NI = 8; }
     else { plan->WM = 1; plan->WN = 4; plan->NI = 4; }
     return true;
-}
-
-hipError_t launch_conv(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
-    switch (p.KT) {
-        case 1: return launch_conv_kt1(p, a, s);
-        case 2: return launch_conv_kt2(p, a, s);
-        case 3: return launch_conv_kt3(p, a, s);
-        case 5: return launch_conv_kt5(p, a, s);
-        case 7: return launch_conv_kt7(p, a, s);
-        case 11: return launch_conv_kt11(p, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-int pair_tile_kt3(int, int);
-int pair_tile_kt5(int, int);
-int pair_tile_kt7(int, int);
-int pair_tile_kt11(int, int);
-hipError_t launch_pair_kt3(const PairArgs&, hipStream_t);
-hipError_t launch_pair_kt5(const PairArgs&, hipStream_t);
-hipError_t launch_pair_kt7(const PairArgs&, hipStream_t);
-hipError_t launch_pair_kt11(const PairArgs&, hipStream_t);
-
-int pair_tile(int k, int C, int dil) {
-    switch (k) {
-        case 3: return pair_tile_kt3(C, dil);
-        case 5: return pair_tile_kt5(C, dil);
-        case 7: return pair_tile_kt7(C, dil);
-        case 11: return pair_tile_kt11(C, dil);
-    }
-    return 0;
-}
-
-hipError_t launch_pair(int k, const PairArgs& a, hipStream_t s) {
-    switch (k) {
-        case 3: return launch_pair_kt3(a, s);
-        case 5: return launch_pair_kt5(a, s);
-        case 7: return launch_pair_kt7(a, s);
-        case 11: return launch_pair_kt11(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-int strip_step_kt3(int, int, int, int*);
-int strip_step_kt5(int, int, int, int*);
-int strip_step_kt7(int, int, int, int*);
-int strip_step_kt11(int, int, int, int*);
-hipError_t launch_strip_kt3(const PairArgs&, hipStream_t);
-hipError_t launch_strip_kt5(const PairArgs&, hipStream_t);
-hipError_t launch_strip_kt7(const PairArgs&, hipStream_t);
-hipError_t launch_strip_kt11(const PairArgs&, hipStream_t);
-
-int strip_step(int k, int C, int dil, int wide, int* wg) {
-    switch (k) {
-        case 3: return strip_step_kt3(C, dil, wide, wg);
-        case 5: return strip_step_kt5(C, dil, wide, wg);
-        case 7: return strip_step_kt7(C, dil, wide, wg);
-        case 11: return strip_step_kt11(C, dil, wide, wg);
-    }
-    return 0;
-}
-
-hipError_t launch_strip(int k, const PairArgs& a, hipStream_t s) {
-    switch (k) {
-        case 3: return launch_strip_kt3(a, s);
-        case 5: return launch_strip_kt5(a, s);
-        case 7: return launch_strip_kt7(a, s);
-        case 11: return launch_strip_kt11(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-int rb_tile_kt3(int, int, int);
-int rb_tile_kt5(int, int, int);
-int rb_tile_kt7(int, int, int);
-int rb_tile_kt11(int, int, int);
-hipError_t launch_rb_kt3(const RbArgs&, int, hipStream_t);
-hipError_t launch_rb_kt5(const RbArgs&, int, hipStream_t);
-hipError_t launch_rb_kt7(const RbArgs&, int, hipStream_t);
-hipError_t launch_rb_kt11(const RbArgs&, int, hipStream_t);
-
-int rb_tile(int k, int C, int max_dil, int wide) {
-    switch (k) {
-        case 3: return rb_tile_kt3(C, max_dil, wide);
-        case 5: return rb_tile_kt5(C, max_dil, wide);
-        case 7: return rb_tile_kt7(C, max_dil, wide);
-        case 11: return rb_tile_kt11(C, max_dil, wide);
-    }
-    return 0;
-}
-
-hipError_t launch_rb(int k, const RbArgs& a, int wide, hipStream_t s) {
-    switch (k) {
-        case 3: return launch_rb_kt3(a, wide, s);
-        case 5: return launch_rb_kt5(a, wide, s);
-        case 7: return launch_rb_kt7(a, wide, s);
-        case 11: return launch_rb_kt11(a, wide, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-int ampb_tile_kt3(int, int, int);
-int ampb_tile_kt5(int, int, int);
-int ampb_tile_kt7(int, int, int);
-int ampb_tile_kt11(int, int, int);
-hipError_t launch_ampb_kt3(const AmpbArgs&, int, hipStream_t);
-hipError_t launch_ampb_kt5(const AmpbArgs&, int, hipStream_t);
-hipError_t launch_ampb_kt7(const AmpbArgs&, int, hipStream_t);
-hipError_t launch_ampb_kt11(const AmpbArgs&, int, hipStream_t);
-
-int ampb_tile(int k, int C, int max_dil, int wide) {
-    switch (k) {
-        case 3: return ampb_tile_kt3(C, max_dil, wide);
-        case 5: return ampb_tile_kt5(C, max_dil, wide);
-        case 7: return ampb_tile_kt7(C, max_dil, wide);
-        case 11: return ampb_tile_kt11(C, max_dil, wide);
-    }
-    return 0;
-}
-
-hipError_t launch_ampb(int k, const AmpbArgs& a, int wide, hipStream_t s) {
-    switch (k) {
-        case 3: return launch_ampb_kt3(a, wide, s);
-        case 5: return launch_ampb_kt5(a, wide, s);
-        case 7: return launch_ampb_kt7(a, wide, s);
-        case 11: return launch_ampb_kt11(a, wide, s);
-    }
-    return hipErrorInvalidValue;
 }
 
 // ---- launch-policy switches: ONE configuration, read from the environment once (first use) and changed afterwards only
@@ -440,22 +349,6 @@ static void strip_geometry(int B, int T, int n1, int hb, int wg_per_cu, int step
 // contractions) neither gain nor lose (profiles/r1_exp_small_tiles.txt).
 constexpr long long kSmallGridWorkgroups = 384;
 
-hipError_t launch_conv_small_kt1(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_small_kt3(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_small_kt5(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_small_kt7(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_small_kt11(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_small(int KT, int ni, int epi, const ConvArgs& a, hipStream_t s) {
-    switch (KT) {
-        case 1: return launch_conv_small_kt1(ni, epi, a, s);
-        case 3: return launch_conv_small_kt3(ni, epi, a, s);
-        case 5: return launch_conv_small_kt5(ni, epi, a, s);
-        case 7: return launch_conv_small_kt7(ni, epi, a, s);
-        case 11: return launch_conv_small_kt11(ni, epi, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 // Frame-rate convs (K = Cin * k short, grids of a few hundred workgroups) run on conv_small_f16x3.hip: whole-K
 // staging, one memory latency instead of one per chunk (same bits as conv_f16x3.hip).
 // amp_set_small_conv(0) keeps them on the pipelined kernel (A/B switch, tests/test_gpu_conv.py).
@@ -465,14 +358,6 @@ static bool small_conv_enabled() { return cfg().small_conv != 0; }
 // transposed convs (2 taps per chunk) and k = 3 convs -- whose GEMM rows are a multiple of 256; same bits as
 // conv_f16x3.hip.  amp_set_conv_blk: 0 off, 1 one 16-channel chunk per staging round, 2 two chunks per
 // round where the kernel has that variant (transposed convs), 3 (default) = 2 + the A-fragment-ring form for k = 7 / 11.
-int conv_blk_nt_kt2(int, int);
-int conv_blk_nt_kt3(int, int);
-int conv_blk_nt_kt7(int, int);
-int conv_blk_nt_kt11(int, int);
-hipError_t launch_conv_blk_kt2(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_blk_kt3(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_blk_kt7(int, int, const ConvArgs&, hipStream_t);
-hipError_t launch_conv_blk_kt11(int, int, const ConvArgs&, hipStream_t);
 static int conv_blk_mode() { return cfg().conv_blk; }
 static int narrow_blk_mode() { return cfg().narrow_blk; }
 // Convs with more than one row group (M > 32 * WM rows: the C = 256 stage, the transposed convs' polyphase rows) launch a
@@ -499,18 +384,6 @@ static int next_rev(const int* lens) {
 }
 // the blocked launch fills the chip only when its (half as many) workgroups still give every CU its two
 constexpr long long kConvBlkMinWorkgroups = 512;
-
-hipError_t launch_conv_f16x3(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
-    switch (p.KT) {
-        case 1: return launch_conv_h_kt1(p, a, s);
-        case 2: return launch_conv_h_kt2(p, a, s);
-        case 3: return launch_conv_h_kt3(p, a, s);
-        case 5: return launch_conv_h_kt5(p, a, s);
-        case 7: return launch_conv_h_kt7(p, a, s);
-        case 11: return launch_conv_h_kt11(p, a, s);
-    }
-    return hipErrorInvalidValue;
-}
 
 }  // namespace amp
 
@@ -714,7 +587,7 @@ static int conv_run(const amp_conv* c, const float* x, int B, int T, float slope
         if (conv_blk_mode() > 0 && plan.NI == 4 && blk_wn > 0 && blk_kt && !c->tanh_out && !c->pad_reflect) {
             int cm = (conv_blk_mode() >= 2 && c->KT == 2 && c->nchunks % 2 == 0) ? 2 : 1;
             const int halo = c->halo_left + c->halo_right;
-            const int nt = blk_wn * (c->KT == 2 ? conv_blk_nt_kt2(cm, halo) : c->KT == 3 ? conv_blk_nt_kt3(cm, halo) : c->KT == 7 ? conv_blk_nt_kt7(cm, halo) : conv_blk_nt_kt11(cm, halo));
+            const int nt = blk_wn * conv_blk_nt(c->KT, cm, halo);
             if (nt > 0 && (long long)B * ((a.Tq + nt - 1) / nt) * (c->M / (256 / blk_wn)) >= kConvBlkMinWorkgroups) { blk_cm = cm; blk_nt = nt; }
         }
         if (plan_small && !(blk_cm == 0 && plan.NI == 2 && small_conv_covers(c) && (c->KT <= 5 || wgs_half <= 128))) return AMP_ERR_UNSUPPORTED;
@@ -723,8 +596,7 @@ static int conv_run(const amp_conv* c, const float* x, int B, int T, float slope
             a.tiles_per_item = (a.Tq + blk_nt - 1) / blk_nt;
             a.wd = blk_nt + c->halo_left + c->halo_right;
             a.row_groups = (conv_rg_fast() && c->M / rows > 1 && conv_weight_bytes(c) <= kConvRgFastMaxWeightBytes) ? c->M / rows : 0;
-            AMP_HIP(c->KT == 2 ? launch_conv_blk_kt2(blk_cm, blk_wn, a, stream) : c->KT == 3 ? launch_conv_blk_kt3(blk_cm, blk_wn, a, stream) :
-                    c->KT == 7 ? launch_conv_blk_kt7(blk_cm, blk_wn, a, stream) : launch_conv_blk_kt11(blk_cm, blk_wn, a, stream));
+            AMP_HIP(launch_conv_blk(c->KT, blk_cm, blk_wn, a, stream));
         } else if (plan.NI == 2 && small_conv_covers(c) && (c->KT <= 5 || wgs_half <= 128)) {
             // a small grid of a short contraction: the whole-K kernel (128 x 32 or 128 x 64 tiles, same bits)
             const int ni = small_conv_ni(c);
@@ -1560,6 +1432,300 @@ int amp_gen_kernel_name(amp_gen* g, int back, int which, char* buf, size_t n) {
 
 #define AMP_RC(expr) do { int rc__ = (expr); if (rc__ != AMP_OK) return rc__; } while (0)
 
+constexpr float kLreluSlope = 0.1f;  // LRELU_SLOPE hifigan.py:14
+
+// One stage of gen_forward_group after its ConvTranspose: what every step of it reads.
+struct Stage {
+    amp_gen* g;
+    int i;                    // stage index
+    int B, t, C, lm;          // items, columns, channels, samples per mel frame (ragged batches: valid length = lens[b] * lm)
+    const int* lens;
+    hipStream_t st;
+    bool conc;                // resblocks 1 .. n_kernels - 1 on g->side streams, with buffers of their own (gen_forward_group)
+    const float* U;           // upsampled stage tensor (input of every resblock)
+    float* XS;                // MRF accumulator: the stage's output
+    float *R, *TMP, *ACT;     // running x inside a resblock, xt between the two convs of a pair, activation output (BigVGAN only)
+    float* SIDE;              // concurrent mode: R, TMP, XS (+ ACT) of resblocks 1 .. n_kernels - 1, side_per buffers of be floats each
+    int side_per;
+    size_t be;
+    const ResBlock& rb(int j) const { return g->rbs[(size_t)i * g->d.n_kernels + j]; }
+};
+
+// MRF mode of resblock j's accumulating launch in the chain of nk resblocks: XS = v, XS += v, ..., XS = (XS + v) / nk
+static int accumulate_mode(int j, int nk) { return j == 0 ? 0 : (j == nk - 1 ? 2 : 1); }
+
+// Resblock j's buffers: its own ones behind the regular buffers when `own` (concurrent mode) and j > 0, else the regular ones
+struct RbBufs { float *R, *TMP, *XS, *ACT; };
+static RbBufs rb_bufs(const Stage& s, int j, bool own) {
+    if (!own || j == 0) return {s.R, s.TMP, s.XS, s.ACT};
+    float* SB = s.SIDE + (size_t)(j - 1) * s.side_per * s.be;
+    return {SB, SB + s.be, SB + 2 * s.be, s.ACT ? SB + 3 * s.be : nullptr};
+}
+
+// XS = ((XS + XS_1) + XS_2 ...) / nk: the MRF mean of resblocks that stored their results separately (in their own XS).  evs: the
+// concurrent mode's events, `st` waits for every side resblock's evs[1 + j] first; null: nothing to wait for.
+static int launch_stage_mrf_sum(const Stage& s, const hipEvent_t* evs) {
+    const int nk = s.g->d.n_kernels;
+    MrfSumArgs ma{};
+    ma.y = s.XS; ma.n = nk - 1; ma.div = (float)nk; ma.count = (size_t)s.B * s.C * s.t;
+    for (int j = 1; j < nk; ++j) {
+        if (evs) AMP_HIP(hipStreamWaitEvent(s.st, evs[1 + j], 0));
+        ma.p[j - 1] = rb_bufs(s, j, true).XS;
+    }
+    AMP_HIP(launch_mrf_sum(ma, s.st));
+    return AMP_OK;
+}
+
+// The horizontal stage forms (try_stage_pair3, try_stage_small3) take a stage of three ResBlock1 whose kernels are 11, 7 and 3 in any order:
+// slot_of[0 / 1 / 2] = the resblock with k = 11 / 7 / 3.  false when the stage is not of that shape.
+static bool horizontal_slots(const Stage& s, int slot_of[3]) {
+    slot_of[0] = slot_of[1] = slot_of[2] = -1;
+    for (int j = 0; j < 3; ++j) {
+        const int k = s.rb(j).c1[0]->k;
+        const int sl = k == 11 ? 0 : k == 7 ? 1 : k == 3 ? 2 : -1;
+        if (sl < 0 || slot_of[sl] >= 0) return false;
+        slot_of[sl] = j;
+    }
+    return true;
+}
+
+// Horizontal form (pair3_f16x3.hip): where the stage's three resblocks run as per-tile fused pairs, pair p of all three shares ONE launch --
+// nd launches + the MRF mean instead of 3 nd launches on three streams with their fork / join events.  Every launch is planned first:
+// *ran = false, nothing launched, when one of the pairs is not a per-tile fused pair.
+static int try_stage_pair3(const Stage& s, const int slot_of[3], bool* ran) {
+    *ran = false;
+    const int nk = s.g->d.n_kernels;
+    const size_t nd = s.rb(0).dil.size();
+    std::vector<Pair3Args> plan(nd);
+    for (int sl = 0; sl < 3; ++sl) {
+        const int j = slot_of[sl];
+        const ResBlock& rb = s.rb(j);
+        if (rb.dil.size() != nd) return AMP_OK;
+        const RbBufs b = rb_bufs(s, j, true);
+        const float* cur = s.U;
+        for (size_t p = 0; p < nd; ++p) {
+            float* dst = p + 1 == nd ? b.XS : (cur == b.R ? b.TMP : b.R);
+            if (!pair_tile_args(rb.c1[p].get(), rb.c2[p].get(), cur, s.B, s.t, kLreluSlope, dst, 0, (float)nk, s.lens, s.lm, &plan[p].a[sl]))
+                return AMP_OK;
+            plan[p].n[sl] = s.B * plan[p].a[sl].tiles_per_item;
+            cur = dst;
+        }
+    }
+    for (const Pair3Args& p : plan) AMP_HIP(launch_pair3(p, s.st));
+    AMP_RC(launch_stage_mrf_sum(s, nullptr));
+    *ran = true;
+    return AMP_OK;
+}
+
+// The same for a stage of UNFUSED whole-K convs (the C = 256 stage of a single utterance): c1 of a dilation, then c2, of all three
+// resblocks in one launch each (conv_small3_f16x3.hip); only the three convs that accumulate into XS stay separate launches, in resblock
+// order with their `=` / `+=` / `(y + v) / n` modes (they add y BEFORE the products: no post-hoc mean).  Every launch is planned first
+// (conv_run with plan_small launches nothing): *ran = false, nothing launched, when one of them is not a whole-K conv.
+static int try_stage_small3(const Stage& s, const int slot_of[3], bool* ran) {
+    *ran = false;
+    const int nk = s.g->d.n_kernels;
+    for (int j = 0; j < 3; ++j)
+        if (pair_supported(s.rb(j).c1[0].get(), s.rb(j).c2[0].get())) return AMP_OK;
+    const size_t nd = s.rb(0).dil.size();
+    struct Step { ConvSmall3Args p; int ni[3]; };
+    std::vector<Step> steps;                        // c1(d_0), c2, c1(d_1), c2, ..., c1(d_last)
+    const float* cur[3] = {s.U, s.U, s.U};
+    RbBufs b[3];
+    for (int j = 0; j < 3; ++j) b[j] = rb_bufs(s, j, true);
+    auto plan3 = [&](bool second, size_t p) -> bool {    // one merged launch: c1[p] (second = false) or c2[p] of the three resblocks
+        Step sp{};
+        for (int sl = 0; sl < 3; ++sl) {
+            const int j = slot_of[sl];
+            const amp_conv* c = second ? s.rb(j).c2[p].get() : s.rb(j).c1[p].get();
+            const int rc = second ? conv_run(c, b[j].TMP, s.B, s.t, 1.f, cur[j], 1.f, b[j].R, 0, 1.f, s.st, 0, s.lens, s.lm, &sp.p.a[sl], &sp.ni[sl])
+                                  : conv_run(c, cur[j], s.B, s.t, kLreluSlope, nullptr, kLreluSlope, b[j].TMP, 0, 1.f, s.st, 0, s.lens, s.lm, &sp.p.a[sl], &sp.ni[sl]);
+            if (rc != AMP_OK) return false;
+            sp.p.nx[sl] = s.B * sp.p.a[sl].tiles_per_item;
+            sp.p.ny[sl] = (sp.p.a[sl].M + 127) / 128;
+        }
+        if (sp.ni[1] != 1 || sp.ni[2] != 1) return false;
+        steps.push_back(sp);
+        return true;
+    };
+    bool ok = true;
+    for (size_t p = 0; ok && p < nd; ++p) {
+        for (int j = 0; j < 3 && ok; ++j) ok = s.rb(j).dil.size() == nd;
+        ok = ok && plan3(false, p);
+        if (ok && p + 1 < nd) {
+            ok = plan3(true, p);
+            for (int j = 0; j < 3; ++j) cur[j] = b[j].R;
+        }
+    }
+    // the accumulating convs must be whole-K launches too
+    for (int j = 0; ok && j < 3; ++j) {
+        ConvArgs unused_a; int unused_ni;
+        ok = conv_run(s.rb(j).c2[nd - 1].get(), b[j].TMP, s.B, s.t, 1.f, cur[j], 1.f, s.XS, accumulate_mode(j, nk), (float)nk, s.st, 0, s.lens,
+                      s.lm, &unused_a, &unused_ni) == AMP_OK;
+    }
+    if (!ok) return AMP_OK;
+    for (const Step& sp : steps) AMP_HIP(launch_conv_small3(sp.p, sp.ni, s.st));
+    for (int j = 0; j < 3; ++j)
+        AMP_RC(conv_run(s.rb(j).c2[nd - 1].get(), b[j].TMP, s.B, s.t, 1.f, cur[j], 1.f, s.XS, accumulate_mode(j, nk), (float)nk, s.st, 0, s.lens, s.lm));
+    *ran = true;
+    return AMP_OK;
+}
+
+// Called right before a resblock's launch that writes XS: in a concurrent chain that launch reads what resblock j - 1 accumulated there and
+// first waits for it (`wait` = evs[j]; null otherwise).
+static int wait_before_last(hipEvent_t wait, hipStream_t sj) {
+    if (wait) AMP_HIP(hipStreamWaitEvent(sj, wait, 0));
+    return AMP_OK;
+}
+
+// ResBlock1 (HiFi-GAN), U -> b.XS on sj with the MRF mode mode_last: the whole resblock in one or two launches, else pair by pair (a fused
+// pair, or its two convs)
+static int run_resblock1(const Stage& s, const ResBlock& rb, const RbBufs& b, int mode_last, hipEvent_t wait, hipStream_t sj) {
+    const int B = s.B, t = s.t;
+    const float nk = (float)s.g->d.n_kernels;
+    if (rb_supported(rb.c1, rb.c2, B, t)) {
+        // the whole resblock in one launch: U -> XS (x and the residual never leave the CU in between) -- or in two, rb_split()
+        const int sp = rb_split(rb.c1, B, t);
+        if (sp > 0) AMP_RC(rb_run(rb.c1, rb.c2, s.U, B, t, kLreluSlope, b.R, 0, 1.f, sj, s.lens, s.lm, 0, sp));
+        AMP_RC(wait_before_last(wait, sj));
+        return rb_run(rb.c1, rb.c2, sp > 0 ? b.R : s.U, B, t, kLreluSlope, b.XS, mode_last, nk, sj, s.lens, s.lm, sp, -1);
+    }
+    const int nd = (int)rb.dil.size();
+    const float* cur = s.U;
+    for (int p = 0; p < nd; ++p) {
+        const bool last = p == nd - 1;
+        const amp_conv *c1 = rb.c1[p].get(), *c2 = rb.c2[p].get();
+        if (pair_supported(c1, c2)) {
+            // the whole pair in one kernel; the output ping-pongs R <-> TMP (never in place: other tiles still read the input's halo)
+            float* dst = last ? b.XS : (cur == b.R ? b.TMP : b.R);
+            if (last) AMP_RC(wait_before_last(wait, sj));
+            AMP_RC(pair_run(c1, c2, cur, B, t, kLreluSlope, dst, last ? mode_last : 0, nk, sj, s.lens, s.lm));
+            cur = dst;
+            continue;
+        }
+        // xt = lrelu(c1(lrelu(x))) ; x = c2(xt) + x        hifigan.py:93-100
+        if (cur == b.TMP) {  // previous pair was fused into TMP: keep the unfused ping-pong legal
+            AMP_HIP(hipMemcpyAsync(b.R, b.TMP, (size_t)B * s.C * t * sizeof(float), hipMemcpyDeviceToDevice, sj));
+            cur = b.R;
+        }
+        AMP_RC(conv_run(c1, cur, B, t, kLreluSlope, nullptr, kLreluSlope, b.TMP, 0, 1.f, sj, 0, s.lens, s.lm));
+        if (!last) { AMP_RC(conv_run(c2, b.TMP, B, t, 1.f, cur, 1.f, b.R, 0, 1.f, sj, 0, s.lens, s.lm)); cur = b.R; }
+        else { AMP_RC(wait_before_last(wait, sj)); AMP_RC(conv_run(c2, b.TMP, B, t, 1.f, cur, 1.f, b.XS, mode_last, nk, sj, 0, s.lens, s.lm)); }
+    }
+    return AMP_OK;
+}
+
+// AMPBlock1 (BigVGAN), U -> b.XS: the whole block in one launch, else per pair act1d, c1, act1d, c2 + residual
+static int run_ampblock1(const Stage& s, const ResBlock& rb, const RbBufs& b, int mode_last, hipEvent_t wait, hipStream_t sj) {
+    const int B = s.B, t = s.t, nd = (int)rb.dil.size();
+    const float nk = (float)s.g->d.n_kernels;
+    if (nd <= AMP_AMPB_MAX_STEPS / 2) {
+        const amp_conv *p1[AMP_AMPB_MAX_STEPS / 2], *p2[AMP_AMPB_MAX_STEPS / 2];
+        for (int p = 0; p < nd; ++p) { p1[p] = rb.c1[p].get(); p2[p] = rb.c2[p].get(); }
+        if (ampb_supported(p1, p2, nd, rb.acts.data(), rb.acts.size(), B, t)) {
+            // the whole AMPBlock in one launch: U -> XS (bigvgan.py:137-146)
+            AMP_RC(wait_before_last(wait, sj));
+            return ampb_run(p1, p2, nd, rb.acts.data(), s.U, B, t, b.XS, mode_last, nk, sj, s.lens, s.lm);
+        }
+    }
+    const float* cur = s.U;   // U, then R: never TMP (no fused pairs here)
+    for (int p = 0; p < nd; ++p) {
+        // xt = c2(a2(c1(a1(x)))) ; x = xt + x              bigvgan.py:137-146
+        const ActParams& a1 = rb.acts[2 * p];
+        const ActParams& a2 = rb.acts[2 * p + 1];
+        AMP_HIP(launch_act1d(cur, b.ACT, B, s.C, t, a1.a_dev, a1.invb_dev, a1.fu_dev, a1.fd_dev, s.lens, s.lm, sj, next_rev(s.lens)));
+        AMP_RC(conv_run(rb.c1[p].get(), b.ACT, B, t, 1.f, nullptr, 1.f, b.TMP, 0, 1.f, sj, 0, s.lens, s.lm));
+        AMP_HIP(launch_act1d(b.TMP, b.ACT, B, s.C, t, a2.a_dev, a2.invb_dev, a2.fu_dev, a2.fd_dev, s.lens, s.lm, sj, next_rev(s.lens)));
+        if (p < nd - 1) { AMP_RC(conv_run(rb.c2[p].get(), b.ACT, B, t, 1.f, cur, 1.f, b.R, 0, 1.f, sj, 0, s.lens, s.lm)); cur = b.R; }
+        else { AMP_RC(wait_before_last(wait, sj)); AMP_RC(conv_run(rb.c2[p].get(), b.ACT, B, t, 1.f, cur, 1.f, b.XS, mode_last, nk, sj, 0, s.lens, s.lm)); }
+    }
+    return AMP_OK;
+}
+
+// ResBlock2 / AMPBlock2, U -> b.XS: x = c(act(x)) + x per dilation          hifigan.py:140-145, bigvgan.py:218-224
+static int run_resblock2(const Stage& s, const ResBlock& rb, const RbBufs& b, int mode_last, hipEvent_t wait, hipStream_t sj) {
+    const bool big = s.g->d.arch == AMP_ARCH_BIGVGAN;
+    const int B = s.B, t = s.t, nd = (int)rb.dil.size();
+    const float* cur = s.U;
+    for (int p = 0; p < nd; ++p) {
+        const float* in = cur;
+        float sl = kLreluSlope;
+        if (big) {
+            const ActParams& a1 = rb.acts[p];
+            AMP_HIP(launch_act1d(cur, b.ACT, B, s.C, t, a1.a_dev, a1.invb_dev, a1.fu_dev, a1.fd_dev, s.lens, s.lm, sj, next_rev(s.lens)));
+            in = b.ACT;
+            sl = 1.f;
+        }
+        if (p < nd - 1) {
+            // the conv reads a halo of `in`; never write the tensor it is reading
+            float* dst = (in == cur && cur == b.R) ? b.TMP : b.R;
+            AMP_RC(conv_run(rb.c1[p].get(), in, B, t, sl, cur, 1.f, dst, 0, 1.f, sj, 0, s.lens, s.lm));
+            cur = dst;
+        } else {
+            AMP_RC(wait_before_last(wait, sj));
+            AMP_RC(conv_run(rb.c1[p].get(), in, B, t, sl, cur, 1.f, b.XS, mode_last, (float)s.g->d.n_kernels, sj, 0, s.lens, s.lm));
+        }
+    }
+    return AMP_OK;
+}
+
+// A stage whose resblocks ALL end in a fused pair / whole-resblock kernel (HiFi-GAN, C <= 128) needs no chain in the concurrent mode: those
+// kernels add the accumulated y to their finished, rounded result, so each resblock stores its own result (mode 0) and one small launch
+// forms ((XS0 + XS1) + XS2) / n afterwards -- the same bits with one join instead of two chained cross-queue waits (~12 us each).
+static bool stage_sums_separately(const Stage& s) {
+    const amp_gen_desc& d = s.g->d;
+    if (!s.conc || d.resblock_type != 1 || d.arch == AMP_ARCH_BIGVGAN || d.n_kernels - 1 > AMP_MRF_MAX_PARTS) return false;
+    for (int j = 0; j < d.n_kernels; ++j) {
+        const ResBlock& rb = s.rb(j);
+        const size_t last = rb.dil.size() - 1;
+        if (!rb_supported(rb.c1, rb.c2, s.B, s.t) && !pair_supported(rb.c1[last].get(), rb.c2[last].get())) return false;
+    }
+    return true;
+}
+
+// profiled forward: every launch of one resblock logs its kernel's name (note_kernel, amp_internal.h)
+struct KernelLogScope {
+    explicit KernelLogScope(std::string* p) { tl_kernel_log = p; if (p) p->clear(); }
+    ~KernelLogScope() { tl_kernel_log = nullptr; }
+};
+
+// The stage's resblocks U -> XS, one after the other on `st` -- or, concurrent mode, resblock 0 on `st` and resblocks 1 .. nk - 1 on the side
+// streams: evs[0] fork, evs[1 + j] = resblock j's accumulating launch done; the launch that accumulates resblock j >= 1 waits for evs[j] and
+// `st` joins on evs[nk] (a chain), or `st` waits for them all and forms the MRF mean itself (stage_sums_separately).  (Measured the other way
+// round too -- the widest resblock on `st`, the others on the side streams: the same 0.81-0.83 ms as a graph replay, but 1.08 instead of
+// 0.90-0.95 ms eager, where the host issues the critical stream's launches last.)  ev_rb / rb_names: the profiled forward's per-resblock
+// events and kernel names.
+static int run_stage_resblocks(const Stage& s, hipEvent_t* ev_rb, std::vector<std::string>* rb_names) {
+    amp_gen* g = s.g;
+    const int nk = g->d.n_kernels;
+    const size_t ev0 = (size_t)s.i * (nk + 1);
+    hipEvent_t* evs = s.conc ? &g->ev_side[ev0] : nullptr;
+    const bool sum_stage = stage_sums_separately(s);
+    if (s.conc) {
+        AMP_HIP(hipEventRecord(evs[0], s.st));
+        for (int j = 1; j < nk; ++j) AMP_HIP(hipStreamWaitEvent(g->side[j - 1], evs[0], 0));
+    }
+    for (int j = 0; j < nk; ++j) {
+        const hipStream_t sj = (s.conc && j > 0) ? g->side[j - 1] : s.st;
+        RbBufs b = rb_bufs(s, j, s.conc);
+        if (!sum_stage) b.XS = s.XS;                                             // a chain: every resblock accumulates into XS
+        const hipEvent_t wait = (s.conc && !sum_stage && j > 0) ? evs[j] : nullptr;
+        const int mode_last = sum_stage ? 0 : accumulate_mode(j, nk);
+        if (ev_rb) AMP_HIP(hipEventRecord(ev_rb[ev0 + j], sj));
+        {
+            KernelLogScope log_scope(rb_names ? &(*rb_names)[(size_t)s.i * nk + j] : nullptr);
+            const ResBlock& rb = s.rb(j);
+            if (g->d.resblock_type != 1) AMP_RC(run_resblock2(s, rb, b, mode_last, wait, sj));
+            else if (g->d.arch == AMP_ARCH_BIGVGAN) AMP_RC(run_ampblock1(s, rb, b, mode_last, wait, sj));
+            else AMP_RC(run_resblock1(s, rb, b, mode_last, wait, sj));
+        }
+        if (s.conc) AMP_HIP(hipEventRecord(evs[1 + j], sj));
+    }
+    if (s.conc && !sum_stage) AMP_HIP(hipStreamWaitEvent(s.st, evs[nk], 0));   // join: the last resblock's accumulating launch follows all the others
+    if (sum_stage) AMP_RC(launch_stage_mrf_sum(s, evs));
+    if (ev_rb) AMP_HIP(hipEventRecord(ev_rb[ev0 + nk], s.st));
+    return AMP_OK;
+}
+
 // One group of `B` items through the whole generator (buffers sized for `be` elements each).
 static int gen_forward_group(amp_gen* g, const float* mel_dev, const float* cond_dev, const int* lens, int B, int T,
                              float* wav_dev, float* base, size_t be, hipStream_t st,
@@ -1571,273 +1737,45 @@ static int gen_forward_group(amp_gen* g, const float* mel_dev, const float* cond
     float* X = base;            // stage input / MRF accumulator (ping-pong with XS)
     float* XS = base + be;
     float* U = base + 2 * be;   // upsampled stage tensor (input of every resblock)
-    float* R = base + 3 * be;   // running x inside a resblock
-    float* TMP = base + 4 * be; // xt between the two convs of a pair
-    float* ACT = big ? base + 5 * be : nullptr;  // anti-aliased activation output
-    float* SIDE = base + (size_t)gen_num_bufs(g) * be;   // concurrent mode: R, TMP, XS (+ ACT) of resblocks 1 .. n_kernels - 1
-    const int side_per = big ? 4 : 3;
+    Stage s{};
+    s.g = g; s.B = B; s.lens = lens; s.st = st; s.conc = conc; s.U = U;
+    s.R = base + 3 * be;
+    s.TMP = base + 4 * be;
+    s.ACT = big ? base + 5 * be : nullptr;
+    s.SIDE = base + (size_t)gen_num_bufs(g) * be;
+    s.side_per = big ? 4 : 3;
+    s.be = be;
     float* CB = base + (size_t)(gen_num_bufs(g) + (conc ? gen_side_bufs(g) : 0)) * be;  // cond(g): [B, C0]
-    const float slope = 0.1f;  // LRELU_SLOPE hifigan.py:14
 
     AMP_RC(conv_run(g->conv_pre.get(), mel_dev, B, T, 1.f, nullptr, 1.f, X, 0, 1.f, st, 0, lens, 1));
     if (cond_dev) {  // x = x + self.cond(g), hifigan.py:426-427 (g has length 1 -> per-channel bias)
         AMP_RC(conv_run(g->cond.get(), cond_dev, B, 1, 1.f, nullptr, 1.f, CB, 0, 1.f, st));
         AMP_HIP(launch_add_channel_bias(X, CB, B, d.upsample_initial_channel, T, st));
     }
+    // the horizontal stage forms: concurrent mode, at most kRbHorizontalMaxFrames mel frames, three ResBlock1 per stage
+    const bool horizontal = conc && (long long)B * T <= kRbHorizontalMaxFrames && d.resblock_type == 1 && !big && d.n_kernels == 3;
     int t = T;
-    int lm = 1;  // samples per mel frame at the current stage (ragged batches: valid length = lens[b] * lm)
-    const int nk = d.n_kernels;
+    int lm = 1;  // samples per mel frame at the current stage
     for (int i = 0; i < d.n_stages; ++i) {
-        const int C = g->ch[i];
         // HiFiGAN: leaky_relu(0.1) before the transposed conv (hifigan.py:206); BigVGAN: none (bigvgan.py:316-318)
-        AMP_RC(conv_run(g->ups[i].get(), X, B, t, big ? 1.f : slope, nullptr, 1.f, U, 0, 1.f, st, 0, lens, lm));
+        AMP_RC(conv_run(g->ups[i].get(), X, B, t, big ? 1.f : kLreluSlope, nullptr, 1.f, U, 0, 1.f, st, 0, lens, lm));
         t *= d.upsample_rates[i];
         lm *= d.upsample_rates[i];
         if (ev_mrf) AMP_HIP(hipEventRecord(ev_mrf[2 * i], st));
-        // concurrent mode: resblock 0 on `st`, resblocks 1 .. nk - 1 on the side streams.  evs[0] fork, evs[1 + j] = resblock j's
-        // accumulating launch done; the launch that accumulates resblock j >= 1 waits for evs[j], `st` joins on evs[nk].  (Measured
-        // the other way round too -- the widest resblock on `st`, the others on the side streams: the same 0.81-0.83 ms as a graph
-        // replay, but 1.08 instead of 0.90-0.95 ms eager, where the host issues the critical stream's launches last.)
-        // Horizontal form (pair3_f16x3.hip): where the stage's three resblocks (k = 11 / 7 / 3) run as per-tile fused pairs, pair p of all
-        // three shares ONE launch -- nd launches + the MRF mean instead of 3 nd launches on three streams with their fork / join events.
-        if (conc && (long long)B * T <= kRbHorizontalMaxFrames && d.resblock_type == 1 && !big && nk == 3) {
-            int slot_of[3] = {-1, -1, -1};                 // resblock index holding k = 11 / 7 / 3
-            bool okh = true;
-            for (int j = 0; j < 3; ++j) {
-                const int k = g->rbs[(size_t)i * nk + j].c1[0]->k;
-                const int sl = k == 11 ? 0 : k == 7 ? 1 : k == 3 ? 2 : -1;
-                if (sl < 0 || slot_of[sl] >= 0) { okh = false; break; }
-                slot_of[sl] = j;
-            }
-            const size_t nd0 = g->rbs[(size_t)i * nk].dil.size();
-            std::vector<Pair3Args> plan(okh ? nd0 : 0);
-            for (int sl = 0; okh && sl < 3; ++sl) {
-                const int j = slot_of[sl];
-                const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-                if (rb.dil.size() != nd0) { okh = false; break; }
-                float* SB = SIDE + (size_t)(j > 0 ? j - 1 : 0) * side_per * be;
-                float* R_ = j > 0 ? SB : R;
-                float* TMP_ = j > 0 ? SB + be : TMP;
-                float* XSJ = j > 0 ? SB + 2 * be : XS;
-                const float* cur = U;
-                for (size_t p = 0; okh && p < nd0; ++p) {
-                    const bool last = p + 1 == nd0;
-                    float* dst = last ? XSJ : (cur == R_ ? TMP_ : R_);
-                    okh = pair_tile_args(rb.c1[p].get(), rb.c2[p].get(), cur, B, t, slope, dst, 0, (float)nk, lens, lm, &plan[p].a[sl]);
-                    if (okh) plan[p].n[sl] = B * plan[p].a[sl].tiles_per_item;
-                    cur = dst;
-                }
-            }
-            if (okh) {
-                for (size_t p = 0; p < nd0; ++p) AMP_HIP(launch_pair3(plan[p], st));
-                MrfSumArgs ma{};
-                ma.y = XS; ma.n = nk - 1; ma.div = (float)nk; ma.count = (size_t)B * C * t;
-                for (int j = 1; j < nk; ++j) ma.p[j - 1] = SIDE + ((size_t)(j - 1) * side_per + 2) * be;
-                AMP_HIP(launch_mrf_sum(ma, st));
-                if (ev_mrf) AMP_HIP(hipEventRecord(ev_mrf[2 * i + 1], st));
-                float* tmp = X; X = XS; XS = tmp;  // x = xs / num_kernels
-                continue;
-            }
+        s.i = i; s.t = t; s.C = g->ch[i]; s.lm = lm; s.XS = XS;
+        bool ran = false;
+        int slot_of[3];
+        if (horizontal && horizontal_slots(s, slot_of)) {
+            AMP_RC(try_stage_pair3(s, slot_of, &ran));
+            if (!ran) AMP_RC(try_stage_small3(s, slot_of, &ran));
         }
-        // The same for a stage of UNFUSED whole-K convs (the C = 256 stage of a single utterance): c1 of a dilation, then c2, of all
-        // three resblocks in one launch each (conv_small3_f16x3.hip); only the three convs that accumulate into XS stay separate
-        // launches, in resblock order with their `=` / `+=` / `(y + v) / n` modes (they add y BEFORE the products: no post-hoc mean).
-        if (conc && (long long)B * T <= kRbHorizontalMaxFrames && d.resblock_type == 1 && !big && nk == 3) {
-            int slot_of[3] = {-1, -1, -1};
-            bool okh = true;
-            for (int j = 0; j < 3; ++j) {
-                const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-                const int k = rb.c1[0]->k;
-                const int sl = k == 11 ? 0 : k == 7 ? 1 : k == 3 ? 2 : -1;
-                if (sl < 0 || slot_of[sl] >= 0 || pair_supported(rb.c1[0].get(), rb.c2[0].get())) { okh = false; break; }
-                slot_of[sl] = j;
-            }
-            const size_t nd0 = g->rbs[(size_t)i * nk].dil.size();
-            struct Step { ConvSmall3Args p; int ni[3]; };
-            std::vector<Step> steps;                        // c1(d_0), c2, c1(d_1), c2, ..., c1(d_last)
-            const float* cur[3] = {U, U, U};
-            float* Rj[3];
-            float* TMPj[3];
-            for (int j = 0; j < 3; ++j) {
-                float* SB = SIDE + (size_t)(j > 0 ? j - 1 : 0) * side_per * be;
-                Rj[j] = j > 0 ? SB : R;
-                TMPj[j] = j > 0 ? SB + be : TMP;
-            }
-            auto plan3 = [&](bool second, size_t p) -> bool {    // one merged launch: c1[p] (second = false) or c2[p] of the three resblocks
-                Step sp{};
-                for (int sl = 0; sl < 3; ++sl) {
-                    const int j = slot_of[sl];
-                    const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-                    const amp_conv* c = second ? rb.c2[p].get() : rb.c1[p].get();
-                    const int rc = second ? conv_run(c, TMPj[j], B, t, 1.f, cur[j], 1.f, Rj[j], 0, 1.f, st, 0, lens, lm, &sp.p.a[sl], &sp.ni[sl])
-                                          : conv_run(c, cur[j], B, t, slope, nullptr, slope, TMPj[j], 0, 1.f, st, 0, lens, lm, &sp.p.a[sl], &sp.ni[sl]);
-                    if (rc != AMP_OK) return false;
-                    sp.p.nx[sl] = B * sp.p.a[sl].tiles_per_item;
-                    sp.p.ny[sl] = (sp.p.a[sl].M + 127) / 128;
-                }
-                if (sp.ni[1] != 1 || sp.ni[2] != 1) return false;
-                steps.push_back(sp);
-                return true;
-            };
-            for (size_t p = 0; okh && p < nd0; ++p) {
-                for (int j = 0; j < 3 && okh; ++j) okh = g->rbs[(size_t)i * nk + j].dil.size() == nd0;
-                okh = okh && plan3(false, p);
-                if (okh && p + 1 < nd0) {
-                    okh = plan3(true, p);
-                    for (int j = 0; j < 3; ++j) cur[j] = Rj[j];
-                }
-            }
-            if (okh) {
-                // the accumulating convs must be whole-K launches too (checked before anything is launched)
-                for (int j = 0; okh && j < 3; ++j) {
-                    ConvArgs tmp_a; int tmp_ni;
-                    const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-                    okh = conv_run(rb.c2[nd0 - 1].get(), TMPj[j], B, t, 1.f, cur[j], 1.f, XS, j == 0 ? 0 : (j == nk - 1 ? 2 : 1), (float)nk, st, 0, lens, lm,
-                                   &tmp_a, &tmp_ni) == AMP_OK;
-                }
-            }
-            if (okh) {
-                for (const Step& sp : steps) AMP_HIP(launch_conv_small3(sp.p, sp.ni, st));
-                for (int j = 0; j < 3; ++j) {
-                    const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-                    AMP_RC(conv_run(rb.c2[nd0 - 1].get(), TMPj[j], B, t, 1.f, cur[j], 1.f, XS, j == 0 ? 0 : (j == nk - 1 ? 2 : 1), (float)nk, st, 0, lens, lm));
-                }
-                if (ev_mrf) AMP_HIP(hipEventRecord(ev_mrf[2 * i + 1], st));
-                float* tmp = X; X = XS; XS = tmp;  // x = xs / num_kernels
-                continue;
-            }
-        }
-        hipEvent_t* evs = conc ? &g->ev_side[(size_t)i * (nk + 1)] : nullptr;
-        // A stage whose resblocks ALL end in a fused pair / whole-resblock kernel (HiFi-GAN, C <= 128) needs no chain: those kernels add
-        // the accumulated y to their finished, rounded result, so each resblock stores its own result (mode 0) and one small launch forms
-        // ((XS0 + XS1) + XS2) / n afterwards -- the same bits with one join instead of two chained cross-queue waits (~12 us each).
-        bool sum_stage = conc && d.resblock_type == 1 && !big && nk - 1 <= AMP_MRF_MAX_PARTS;
-        for (int j = 0; sum_stage && j < nk; ++j) {
-            const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-            const size_t last = rb.dil.size() - 1;
-            sum_stage = rb_supported(rb.c1, rb.c2, B, t) || pair_supported(rb.c1[last].get(), rb.c2[last].get());
-        }
-        if (conc) {
-            AMP_HIP(hipEventRecord(evs[0], st));
-            for (int j = 1; j < nk; ++j) AMP_HIP(hipStreamWaitEvent(g->side[j - 1], evs[0], 0));
-        }
-        for (int j = 0; j < nk; ++j) {
-            const bool on_side = conc && j > 0;
-            hipStream_t sj = on_side ? g->side[j - 1] : st;
-            float* SB = SIDE + (size_t)(on_side ? j - 1 : 0) * side_per * be;
-            float* R_ = on_side ? SB : R;
-            float* TMP_ = on_side ? SB + be : TMP;
-            float* XSJ = (on_side && sum_stage) ? SB + 2 * be : XS;      // where this resblock's result goes
-            float* ACT_ = (on_side && big) ? SB + 3 * be : ACT;
-            // called right before the launch that writes XS: it reads what resblock j - 1 accumulated there
-            auto before_last = [&]() -> int {
-                if (conc && !sum_stage && j > 0) AMP_HIP(hipStreamWaitEvent(sj, evs[j], 0));
-                return AMP_OK;
-            };
-            if (ev_rb) AMP_HIP(hipEventRecord(ev_rb[(size_t)i * (nk + 1) + j], sj));
-            auto resblock = [&]() -> int {
-            // profiled forward: every launch of this resblock logs its kernel's name (note_kernel, amp_internal.h)
-            struct LogScope { LogScope(std::string* p) { tl_kernel_log = p; if (p) p->clear(); } ~LogScope() { tl_kernel_log = nullptr; } }
-                log_scope(rb_names ? &(*rb_names)[(size_t)i * nk + j] : nullptr);
-            const ResBlock& rb = g->rbs[(size_t)i * nk + j];
-            const int nd = (int)rb.dil.size();
-            const int mode_last = (nk == 1 || sum_stage) ? 0 : (j == 0 ? 0 : (j == nk - 1 ? 2 : 1));
-            const float* cur = U;
-            if (d.resblock_type == 1 && !big && rb_supported(rb.c1, rb.c2, B, t)) {
-                // the whole resblock in one launch: U -> XSJ (x and the residual never leave the CU in between) -- or in two, rb_split()
-                const int sp = rb_split(rb.c1, B, t);
-                if (sp > 0) AMP_RC(rb_run(rb.c1, rb.c2, U, B, t, slope, R_, 0, 1.f, sj, lens, lm, 0, sp));
-                AMP_RC(before_last());
-                AMP_RC(rb_run(rb.c1, rb.c2, sp > 0 ? R_ : U, B, t, slope, XSJ, mode_last, (float)nk, sj, lens, lm, sp, -1));
-                return AMP_OK;
-            }
-            if (d.resblock_type == 1 && big && nd <= AMP_AMPB_MAX_STEPS / 2) {
-                const amp_conv *p1[AMP_AMPB_MAX_STEPS / 2], *p2[AMP_AMPB_MAX_STEPS / 2];
-                for (int p = 0; p < nd; ++p) { p1[p] = rb.c1[p].get(); p2[p] = rb.c2[p].get(); }
-                if (ampb_supported(p1, p2, nd, rb.acts.data(), rb.acts.size(), B, t)) {
-                    // the whole AMPBlock in one launch: U -> XSJ (bigvgan.py:137-146)
-                    AMP_RC(before_last());
-                    AMP_RC(ampb_run(p1, p2, nd, rb.acts.data(), U, B, t, XSJ, mode_last, (float)nk, sj, lens, lm));
-                    return AMP_OK;
-                }
-            }
-            for (int p = 0; p < nd; ++p) {
-                const bool last = p == nd - 1;
-                if (d.resblock_type == 1) {
-                    if (!big && pair_supported(rb.c1[p].get(), rb.c2[p].get())) {
-                        // the whole pair in one kernel; the output ping-pongs R_ <-> TMP_ (never in place:
-                        // other tiles still read the input's halo)
-                        float* dst = last ? XSJ : (cur == R_ ? TMP_ : R_);
-                        if (last) AMP_RC(before_last());
-                        AMP_RC(pair_run(rb.c1[p].get(), rb.c2[p].get(), cur, B, t, slope, dst, last ? mode_last : 0, (float)nk, sj, lens, lm));
-                        cur = dst;
-                    } else if (!big) {
-                        // xt = lrelu(c1(lrelu(x))) ; x = c2(xt) + x        hifigan.py:93-100
-                        if (cur == TMP_) {  // previous pair was fused into TMP_: keep the unfused ping-pong legal
-                            AMP_HIP(hipMemcpyAsync(R_, TMP_, (size_t)B * C * t * sizeof(float), hipMemcpyDeviceToDevice, sj));
-                            cur = R_;
-                        }
-                        AMP_RC(conv_run(rb.c1[p].get(), cur, B, t, slope, nullptr, slope, TMP_, 0, 1.f, sj, 0, lens, lm));
-                        if (!last) { AMP_RC(conv_run(rb.c2[p].get(), TMP_, B, t, 1.f, cur, 1.f, R_, 0, 1.f, sj, 0, lens, lm)); cur = R_; }
-                        else { AMP_RC(before_last()); AMP_RC(conv_run(rb.c2[p].get(), TMP_, B, t, 1.f, cur, 1.f, XSJ, mode_last, (float)nk, sj, 0, lens, lm)); }
-                    } else {
-                        // xt = c2(a2(c1(a1(x)))) ; x = xt + x              bigvgan.py:137-146
-                        const ActParams& a1 = rb.acts[2 * p];
-                        const ActParams& a2 = rb.acts[2 * p + 1];
-                        AMP_HIP(launch_act1d(cur, ACT_, B, C, t, a1.a_dev, a1.invb_dev, a1.fu_dev, a1.fd_dev, lens, lm, sj, next_rev(lens)));
-                        if (cur == TMP_) {  // a previous pair was fused into TMP_: keep the unfused ping-pong legal
-                            AMP_HIP(hipMemcpyAsync(R_, TMP_, (size_t)B * C * t * sizeof(float), hipMemcpyDeviceToDevice, sj));
-                            cur = R_;
-                        }
-                        AMP_RC(conv_run(rb.c1[p].get(), ACT_, B, t, 1.f, nullptr, 1.f, TMP_, 0, 1.f, sj, 0, lens, lm));
-                        AMP_HIP(launch_act1d(TMP_, ACT_, B, C, t, a2.a_dev, a2.invb_dev, a2.fu_dev, a2.fd_dev, lens, lm, sj, next_rev(lens)));
-                        const float* c2_in = ACT_;
-                        if (!last) { AMP_RC(conv_run(rb.c2[p].get(), c2_in, B, t, 1.f, cur, 1.f, R_, 0, 1.f, sj, 0, lens, lm)); cur = R_; }
-                        else { AMP_RC(before_last()); AMP_RC(conv_run(rb.c2[p].get(), c2_in, B, t, 1.f, cur, 1.f, XSJ, mode_last, (float)nk, sj, 0, lens, lm)); }
-                    }
-                } else {
-                    // x = c(act(x)) + x                                    hifigan.py:140-145, bigvgan.py:218-224
-                    const float* in = cur;
-                    float sl = slope;
-                    if (big) {
-                        const ActParams& a1 = rb.acts[p];
-                        AMP_HIP(launch_act1d(cur, ACT_, B, C, t, a1.a_dev, a1.invb_dev, a1.fu_dev, a1.fd_dev, lens, lm, sj, next_rev(lens)));
-                        in = ACT_;
-                        sl = 1.f;
-                    }
-                    if (!last) {
-                        // the conv reads a halo of `in`; never write the tensor it is reading
-                        float* dst = (in == cur && cur == R_) ? TMP_ : R_;
-                        AMP_RC(conv_run(rb.c1[p].get(), in, B, t, sl, cur, 1.f, dst, 0, 1.f, sj, 0, lens, lm));
-                        cur = dst;
-                    } else {
-                        AMP_RC(before_last());
-                        AMP_RC(conv_run(rb.c1[p].get(), in, B, t, sl, cur, 1.f, XSJ, mode_last, (float)nk, sj, 0, lens, lm));
-                    }
-                }
-            }
-            return AMP_OK;
-            };
-            AMP_RC(resblock());
-            if (conc) AMP_HIP(hipEventRecord(evs[1 + j], sj));
-        }
-        if (conc && !sum_stage) AMP_HIP(hipStreamWaitEvent(st, evs[nk], 0));   // join: the last resblock's accumulating launch follows all the others
-        if (sum_stage) {
-            MrfSumArgs ma{};
-            ma.y = XS; ma.n = nk - 1; ma.div = (float)nk; ma.count = (size_t)B * C * t;
-            for (int j = 1; j < nk; ++j) {
-                AMP_HIP(hipStreamWaitEvent(st, evs[1 + j], 0));
-                ma.p[j - 1] = SIDE + ((size_t)(j - 1) * side_per + 2) * be;
-            }
-            AMP_HIP(launch_mrf_sum(ma, st));
-        }
-        if (ev_rb) AMP_HIP(hipEventRecord(ev_rb[(size_t)i * (nk + 1) + nk], st));
+        if (!ran) AMP_RC(run_stage_resblocks(s, ev_rb, rb_names));
         if (ev_mrf) AMP_HIP(hipEventRecord(ev_mrf[2 * i + 1], st));
         float* tmp = X; X = XS; XS = tmp;  // x = xs / num_kernels
     }
     if (big) {
-        AMP_HIP(launch_act1d(X, ACT, B, g->post_cin, t, g->act_post.a_dev, g->act_post.invb_dev, g->act_post.fu_dev, g->act_post.fd_dev, lens, lm, st, next_rev(lens)));
-        AMP_HIP(launch_conv_post(ACT, g->post_w_dev, g->post_b_dev, wav_dev, B, g->post_cin, t, 7, 1.f, 1, lens, lm, st));
+        AMP_HIP(launch_act1d(X, s.ACT, B, g->post_cin, t, g->act_post.a_dev, g->act_post.invb_dev, g->act_post.fu_dev, g->act_post.fd_dev, lens, lm, st, next_rev(lens)));
+        AMP_HIP(launch_conv_post(s.ACT, g->post_w_dev, g->post_b_dev, wav_dev, B, g->post_cin, t, 7, 1.f, 1, lens, lm, st));
     } else {
         // F.leaky_relu(x) with the DEFAULT slope 0.01 (hifigan.py:215,439), conv_post, tanh
         AMP_HIP(launch_conv_post(X, g->post_w_dev, g->post_b_dev, wav_dev, B, g->post_cin, t, 7, 0.01f, 1, lens, lm, st));

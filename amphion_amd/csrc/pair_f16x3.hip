@@ -46,12 +46,9 @@ static hipError_t launch_pair_one(const PairArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // Output columns per workgroup for C channels, or 0 when (C, KT, dilation) is not covered.
-int AMP_CAT(pair_tile_kt, AMP_KT)(int C, int dil) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+int pair_tile(int C, int dil) {
     const int span = (KT - 1) * dil;   // 2 * h1
     if (C == 128) return (96 + span <= 192) ? 96 - (KT - 1) : 0;
     if (C == 64) return (128 + span <= 192) ? 128 - (KT - 1) : 0;
@@ -59,12 +56,15 @@ int AMP_CAT(pair_tile_kt, AMP_KT)(int C, int dil) {
     return 0;
 }
 
-hipError_t AMP_CAT(launch_pair_kt, AMP_KT)(const PairArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_pair(const PairArgs& a, hipStream_t stream) {
     if (a.C == 128) return launch_pair_one<KT, 4, 1, 3, 192>(a, stream);
     if (a.C == 64) return launch_pair_one<KT, 2, 2, 2, 192>(a, stream);
     if (a.C == 32) return launch_pair_one<KT, 1, 4, 2, 320>(a, stream);
     return hipErrorInvalidValue;
 }
+
+template int pair_tile<AMP_KT>(int, int);
+template hipError_t launch_pair<AMP_KT>(const PairArgs&, hipStream_t);
 
 }  // namespace amp

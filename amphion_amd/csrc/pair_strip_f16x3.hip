@@ -465,29 +465,29 @@ static hipError_t launch_strip_one(const PairArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // Step width (xt columns = output columns per step) for C channels, or 0 when (C, KT, dilation) is not covered;
 // *wg_per_cu = resident workgroups per CU (LDS / register bound), used by the host to size the strips.
 // ONE form is left (round 5): wide = 3, the 2 x 2-blocked strips with an A-fragment ring -- C = 128, k >= 7: 4 waves x (64 rows x 128 columns),
 // 256-column steps, one workgroup per CU -- the form the launch policy picks.  The four-wave strips (C = 32 / 64 / 128, two workgroups per CU:
 // +1.5 % at C = 128, k = 11, slower elsewhere) and the eight-wave C = 256 strips (overtaken by the row-blocked conv kernel) were reachable
 // only through amp_set_pair_strips(1) and are gone, like round 2's double-width tiles, the whole-chunk 2 x 2 form and the C = 64 ring form.
-int AMP_CAT(strip_step_kt, AMP_KT)(int C, int dil, int wide, int* wg_per_cu) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+int strip_step(int C, int dil, int wide, int* wg_per_cu) {
     const int span = (KT - 1) * dil;   // staged halo = 2 * h1
     if (wg_per_cu) *wg_per_cu = 1;
     if (wide == 3 && C == 128) return (KT >= 7 && 256 + span <= 320) ? 256 : 0;
     return 0;
 }
 
-hipError_t AMP_CAT(launch_strip_kt, AMP_KT)(const PairArgs& a, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_strip(const PairArgs& a, hipStream_t stream) {
     if constexpr (KT >= 7) {
         if (a.wide == 3 && a.C == 128) return launch_strip_one<KT, 2, 2, 4, 320, 2, 4, 1>(a, stream);
     }
     return hipErrorInvalidValue;
 }
+
+template int strip_step<AMP_KT>(int, int, int, int*);
+template hipError_t launch_strip<AMP_KT>(const PairArgs&, hipStream_t);
 
 }  // namespace amp

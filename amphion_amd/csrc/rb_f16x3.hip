@@ -299,13 +299,10 @@ static hipError_t launch_rb_one(const RbArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define AMP_CAT2(a, b) a##b
-#define AMP_CAT(a, b) AMP_CAT2(a, b)
-
 // Tile width W (columns evaluated per workgroup; outputs per tile = W - 2 * rh) for C channels in form `wide`
 // (1: eight waves, one workgroup per CU; 0: four waves, two per CU -- C = 32, and C = 64 at k <= 5 since round 6), or 0 when not covered.
-int AMP_CAT(rb_tile_kt, AMP_KT)(int C, int max_dil, int wide) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+int rb_tile(int C, int max_dil, int wide) {
     const int reach = (KT - 1) / 2 * max_dil;
     if (reach > 32) return 0;
     if (C == 32) return wide ? 1024 : 512;
@@ -314,8 +311,8 @@ int AMP_CAT(rb_tile_kt, AMP_KT)(int C, int max_dil, int wide) {
     return 0;
 }
 
-hipError_t AMP_CAT(launch_rb_kt, AMP_KT)(const RbArgs& a, int wide, hipStream_t stream) {
-    constexpr int KT = AMP_KT;
+template <int KT>
+hipError_t launch_rb(const RbArgs& a, int wide, hipStream_t stream) {
     constexpr int RING = KT >= 7 ? 4 : 0;
     if (a.C == 32) return wide ? launch_rb_one<KT, 1, 8, 4, RING>(a, stream) : launch_rb_one<KT, 1, 4, 4, RING>(a, stream);
     if (a.C == 64 && wide) return launch_rb_one<KT, 2, 4, 4, RING>(a, stream);
@@ -328,5 +325,8 @@ hipError_t AMP_CAT(launch_rb_kt, AMP_KT)(const RbArgs& a, int wide, hipStream_t 
 
     return hipErrorInvalidValue;
 }
+
+template int rb_tile<AMP_KT>(int, int, int);
+template hipError_t launch_rb<AMP_KT>(const RbArgs&, int, hipStream_t);
 
 }  // namespace amp
