@@ -307,13 +307,14 @@ inline void note_work(unsigned long long workgroups, double gflop, double mb, co
     manifest_add(tl_last_kernel, workgroups, gflop, mb, what);
 }
 // a Conv1d / ConvTranspose1d launch: GEMM M = Cout * up rows, K = Cin * KT, N = B * Tq columns; bytes = x read once + y written once
-// (+ the residual / running sum read)
+// (+ the residual / running sum read).  `grid=XxY` states the launch's grid: Y > 1 is the 2-D order (row group = blockIdx.y), Y = 1 with
+// several row groups the row-group-fastest 1-D order (ConvArgs::row_groups)
 inline void note_conv_work(const ConvArgs& a, int KT, dim3 grid) {
     if (!manifest_on()) return;
     const double gf = 2.0 * a.M * a.Cin * KT * (double)a.Tq * a.B / 1e9;
     const double mb = 4.0 * a.B * ((double)a.Cin * a.Tin + (double)a.Cout * a.Tout * (1 + (a.res ? 1 : 0) + (a.mode ? 1 : 0))) / 1e6;
-    note_work((unsigned long long)grid.x * grid.y, gf, mb, "%s %d->%d k=%d d=%d T=%d->%d B=%d%s%s", a.up > 1 ? "ConvT" : "conv", a.Cin, a.Cout,
-              a.up > 1 ? KT * a.up : KT, a.dstep, a.Tin, a.Tout, a.B, a.res ? " +res" : "", a.mode ? " +sum" : "");
+    note_work((unsigned long long)grid.x * grid.y, gf, mb, "%s %d->%d k=%d d=%d T=%d->%d B=%d%s%s grid=%ux%u", a.up > 1 ? "ConvT" : "conv", a.Cin,
+              a.Cout, a.up > 1 ? KT * a.up : KT, a.dstep, a.Tin, a.Tout, a.B, a.res ? " +res" : "", a.mode ? " +sum" : "", grid.x, grid.y);
 }
 
 // The f16x3 kernels stage fp32 activations as hi + lo f16 pairs after an exact x16: anything beyond |x| = 4094 (or

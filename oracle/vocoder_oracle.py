@@ -492,6 +492,45 @@ def bigvgan_base_hp():
     return hp
 
 
+def bigvgan_large_hp():
+    """egs/vocoder/gan/bigvgan_large/exp_config.json:15-56 (n_mel 100 from egs/vocoder/gan/exp_config_base.json:54)."""
+    return dict(
+        resblock="1",
+        activation="snakebeta",
+        snake_logscale=True,
+        upsample_rates=[4, 4, 2, 2, 2, 2],
+        upsample_kernel_sizes=[8, 8, 4, 4, 4, 4],
+        upsample_initial_channel=1536,
+        resblock_kernel_sizes=[3, 7, 11],
+        resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+    )
+
+
+def tfr_hifigan_hp():
+    """egs/vocoder/gan/tfr_enhanced_hifigan/exp_config.json:44-81 (n_mel 100: :32)."""
+    return dict(
+        resblock="1",
+        upsample_rates=[8, 4, 2, 2, 2],
+        upsample_kernel_sizes=[16, 8, 4, 4, 4],
+        upsample_initial_channel=768,
+        resblock_kernel_sizes=[3, 5, 7],
+        resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+    )
+
+
+def nsfhifigan_recipe_hp():
+    """egs/vocoder/gan/nsfhifigan/exp_config.json:17-55 (n_mel 100 from egs/vocoder/gan/exp_config_base.json:54)."""
+    return dict(
+        resblock="1",
+        harmonic_num=8,
+        upsample_rates=[8, 4, 2, 2, 2],
+        upsample_kernel_sizes=[16, 8, 4, 4, 4],
+        upsample_initial_channel=768,
+        resblock_kernel_sizes=[3, 7, 11],
+        resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+    )
+
+
 def preprocess_22k():
     """config/fs2.json:25-31."""
     return SimpleNamespace(sample_rate=22050, n_fft=1024, win_size=1024, hop_size=256, n_mel=80, fmin=0, fmax=8000)
