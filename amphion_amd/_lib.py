@@ -22,6 +22,7 @@ AMP_ACT_LRELU, AMP_ACT_SNAKE, AMP_ACT_SNAKEBETA = 0, 1, 2
 AMP_PRECISION_F32, AMP_PRECISION_F16X3 = 0, 1
 AMP_CONV_OPT_PAD_REFLECT, AMP_CONV_OPT_TANH = 1, 2
 AMP_PAD_REPLICATE, AMP_PAD_ZEROS, AMP_PAD_REFLECT = 0, 1, 2
+AMP_PW_BIAS, AMP_PW_BIAS_GELU, AMP_PW_SCALE_RES = 0, 1, 2
 PRECISIONS = {"f32": AMP_PRECISION_F32, "fp32": AMP_PRECISION_F32, "f16x3": AMP_PRECISION_F16X3}
 
 
@@ -105,6 +106,12 @@ _SIGNATURES = {
     "amp_conv_forward_mrf": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "amp_apnet_polar": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "amp_istft_same": (c_int, [POINTER(amp_mel_desc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_istft_same_polar": (c_int, [POINTER(amp_mel_desc), c_void_p, ctypes.c_longlong, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "amp_pw_create": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_pw_forward": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_pw_precision": (c_int, [c_void_p]),
+    "amp_pw_destroy": (None, [c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),

@@ -1116,8 +1116,21 @@ hipError_t launch_mel(const amp_mel_desc& d, const float* wav, const int* lens, 
 //   frame_f[n] = irfft(mag_f * e^{i phase_f})[n] * window[n] * hop/n_fft        (kernel 1, FFT in LDS)
 //   out[m]     = (n_fft/hop) * sum_f frame_f[m - f*hop] / wss[m]   where wss[m] > tiny      (kernel 2)
 // ------------------------------------------------------------------------------------------------
+// The third input form (polar == 2): the [B, 2 * bins, F] output of Vocos's ISTFTHead.out Linear read in place (vocos.py:346-359):
+//   mag = min(exp(row k), clip), X[k] = mag * (cos p, sin p) with p = row bins + k
+// exp overflowing to inf clips to `clip` as torch.clip does (a NaN stays NaN); sincosf's full range reduction: the phases are
+// unbounded Linear outputs.
+__device__ __forceinline__ void istft_head_bin(const float* __restrict__ head, size_t o, size_t phase_off, float clip, float& re, float& im) {
+    float m = expf(head[o]);
+    m = m > clip ? clip : m;
+    float sn, cs;
+    sincosf(head[o + phase_off], &sn, &cs);
+    re = m * cs;
+    im = m * sn;
+}
+
 __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restrict__ mag, const float* __restrict__ phase,
-                                                           int polar, int F, int n_fft, int log2n, float inv_scale,
+                                                           int polar, long long hbs, float clip, int F, int n_fft, int log2n, float inv_scale,
                                                            const float* __restrict__ window, float* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* buf0 = reinterpret_cast<float2*>(smem);   // [n_fft]
@@ -1132,7 +1145,9 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
     for (int k = tid; k < bins; k += 256) {
         const size_t o = ((size_t)b * bins + k) * F + f;
         float re, im;
-        if (polar) {          // (magnitude, phase)
+        if (polar == 2) {     // Vocos head: log-magnitude rows [0, bins), phase rows [bins, 2 bins) of one [2 bins, F] slab per item
+            istft_head_bin(mag, (size_t)b * hbs + (size_t)k * F + f, (size_t)bins * F, clip, re, im);
+        } else if (polar) {   // (magnitude, phase)
             const float m = mag[o];
             float sn, cs;
             sincosf(phase[o], &sn, &cs);
@@ -1178,7 +1193,7 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
 // The same for any other n_fft (round 5: the inverse of mel_mixed_kernel's transform): mixed-radix Stockham passes over
 // the Hermitian extension; an odd n_fft has no Nyquist bin (bins = (n_fft - 1) / 2 + 1, every k >= 1 has a partner n_fft - k).
 __global__ __launch_bounds__(256) void istft_frames_mixed_kernel(const float* __restrict__ mag, const float* __restrict__ phase,
-                                                                 int polar, int F, int n_fft, const MelRadices rad, float inv_scale,
+                                                                 int polar, long long hbs, float clip, int F, int n_fft, const MelRadices rad, float inv_scale,
                                                                  const float* __restrict__ window, float* __restrict__ frames) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* buf0 = reinterpret_cast<float2*>(smem);   // [n_fft]
@@ -1193,7 +1208,9 @@ __global__ __launch_bounds__(256) void istft_frames_mixed_kernel(const float* __
     for (int k = tid; k < bins; k += 256) {
         const size_t o = ((size_t)b * bins + k) * F + f;
         float re, im;
-        if (polar) {
+        if (polar == 2) {
+            istft_head_bin(mag, (size_t)b * hbs + (size_t)k * F + f, (size_t)bins * F, clip, re, im);
+        } else if (polar) {
             const float m = mag[o];
             float sn, cs;
             sincosf(phase[o], &sn, &cs);
@@ -1243,7 +1260,7 @@ __global__ __launch_bounds__(256) void istft_frames_mixed_kernel(const float* __
 // times the window and inv_scale.  (irfft ignores Im X[0] and Im X[M]: zero rows of the pseudo-inverse basis.)
 template <int P>
 __global__ __launch_bounds__(64 * MEL_WAVES, 2) void istft_wave_kernel(const float* __restrict__ mag, const float* __restrict__ phase, int polar,
-                                                                     int F, long long nframes, float inv_scale,
+                                                                     long long hbs, float clip, int F, long long nframes, float inv_scale,
                                                                      const float* __restrict__ window, float* __restrict__ frames) {
     constexpr int M = MelW<P>::M, N = MelW<P>::N, BINS = MelW<P>::BINS, XW = MelW<P>::XW;
     constexpr int I8 = 8 * P, NU = (I8 + 63) / 64;
@@ -1270,7 +1287,9 @@ __global__ __launch_bounds__(64 * MEL_WAVES, 2) void istft_wave_kernel(const flo
         auto load_bin = [&](int k) {
             const size_t o = ((size_t)b * BINS + k) * F + f;
             float re, im;
-            if (polar) {
+            if (polar == 2) {
+                istft_head_bin(mag, (size_t)b * hbs + (size_t)k * F + f, (size_t)BINS * F, clip, re, im);
+            } else if (polar) {
                 const float m = mag[o];
                 float sn, cs;
                 sincosf(phase[o], &sn, &cs);
@@ -1348,25 +1367,25 @@ __global__ __launch_bounds__(64 * MEL_WAVES, 2) void istft_wave_kernel(const flo
 }
 
 template <int P>
-static hipError_t launch_istft_wave(const float* a, const float* b, int polar, int B, int F, float inv_scale, const float* window, float* frames,
-                                    hipStream_t stream) {
+static hipError_t launch_istft_wave(const float* a, const float* b, int polar, long long hbs, float clip, int B, int F, float inv_scale,
+                                    const float* window, float* frames, hipStream_t stream) {
     const size_t lds = ((size_t)MelW<P>::N + (size_t)MEL_WAVES * MelW<P>::XW) * sizeof(float2);
     if (hipError_t e = ensure_dynamic_lds<&istft_wave_kernel<P>>(lds); e != hipSuccess) return e;
     const long long nframes = (long long)B * F;
-    hipLaunchKernelGGL(istft_wave_kernel<P>, dim3((unsigned)((nframes + MEL_FPB - 1) / MEL_FPB)), dim3(64 * MEL_WAVES), lds, stream, a, b, polar, F,
-                       nframes, inv_scale, window, frames);
+    hipLaunchKernelGGL(istft_wave_kernel<P>, dim3((unsigned)((nframes + MEL_FPB - 1) / MEL_FPB)), dim3(64 * MEL_WAVES), lds, stream, a, b, polar, hbs, clip,
+                       F, nframes, inv_scale, window, frames);
     return hipGetLastError();
 }
 
 // irfft(spectrum) * window * inv_scale / n_fft per frame: the radix-2 kernel for powers of two, the mixed-radix one otherwise
 static hipError_t launch_istft_frames(int n_fft, const float* a, const float* b, int polar, int B, int F, float inv_scale, const float* window,
-                                      float* frames, hipStream_t stream) {
+                                      float* frames, hipStream_t stream, long long hbs = 0, float clip = 0.f) {
     // n_fft = 1920: the wave-per-frame kernel (needs 8-byte aligned frames and window: hipMalloc'ed tensors always are).  Measured, same box, alternating
     // (profiles/r6_b_mel_wave_kernel.txt): STFT.inverse of 64 x 137 frames 0.272 -> 0.177 ms.  For powers of two it is level with the radix-2 kernel
     // (512 / 1024 / 2048: 0.129 / 0.134 / 0.175 against 0.131 / 0.129 / 0.160 ms): the inverse is bound by its strided spectrum reads, the frame round trip
     // through HBM and the overlap-add pass, not by the transform -- those lengths stay where they were.
     if (n_fft == 1920 && (reinterpret_cast<uintptr_t>(window) & 7) == 0 && (reinterpret_cast<uintptr_t>(frames) & 7) == 0)
-        return launch_istft_wave<15>(a, b, polar, B, F, inv_scale, window, frames, stream);
+        return launch_istft_wave<15>(a, b, polar, hbs, clip, B, F, inv_scale, window, frames, stream);
     if ((n_fft & (n_fft - 1)) == 0) {
         int log2n = 0;
         while ((1 << log2n) < n_fft) ++log2n;
@@ -1374,14 +1393,14 @@ static hipError_t launch_istft_frames(int n_fft, const float* a, const float* b,
         if (lds > 64 * 1024) {
             if (hipError_t e = ensure_dynamic_lds<&istft_frames_kernel>(96 * 1024); e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)((size_t)B * F)), dim3(256), lds, stream, a, b, polar, F, n_fft, log2n, inv_scale, window, frames);
+        hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)((size_t)B * F)), dim3(256), lds, stream, a, b, polar, hbs, clip, F, n_fft, log2n, inv_scale, window, frames);
         return hipGetLastError();
     }
     MelRadices rad;
     if (!mel_radices(n_fft, &rad)) return hipErrorInvalidValue;
     const size_t lds = (size_t)(3 * n_fft) * sizeof(float2);
     if (hipError_t e = ensure_dynamic_lds<&istft_frames_mixed_kernel>(112 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(istft_frames_mixed_kernel, dim3((unsigned)((size_t)B * F)), dim3(256), lds, stream, a, b, polar, F, n_fft, rad, inv_scale, window, frames);
+    hipLaunchKernelGGL(istft_frames_mixed_kernel, dim3((unsigned)((size_t)B * F)), dim3(256), lds, stream, a, b, polar, hbs, clip, F, n_fft, rad, inv_scale, window, frames);
     return hipGetLastError();
 }
 
@@ -1406,10 +1425,11 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
 
 // mode 0: STFT.inverse (stft.py:183-222): polar input, crop n_fft/2, out = scale * sum / wss where wss > tiny
 // mode 1: APNet ISTFT "same" (apnet.py:46-101): re/im input, crop (win - hop)/2, out = sum / envelope, L = F * hop
+// head_bs > 0 (mode 1 only): `a` is Vocos's ISTFTHead Linear output [B, 2 * bins, F] with batch stride head_bs, b is unused (polar == 2)
 hipError_t launch_istft(const amp_mel_desc& d, int mode, const float* a, const float* b, int B, int F, const float* window,
-                        const float* wss, float* frames, float* wav, hipStream_t stream) {
+                        const float* wss, float* frames, float* wav, hipStream_t stream, long long head_bs = 0, float mag_clip = 0.f) {
     const float scale = mode == 0 ? (float)d.n_fft / (float)d.hop_size : 1.0f;
-    hipError_t e = launch_istft_frames(d.n_fft, a, b, mode == 0 ? 1 : 0, B, F, 1.0f / scale, window, frames, stream);
+    hipError_t e = launch_istft_frames(d.n_fft, a, b, head_bs > 0 ? 2 : mode == 0 ? 1 : 0, B, F, 1.0f / scale, window, frames, stream, head_bs, mag_clip);
     if (e != hipSuccess) return e;
     const int crop = mode == 0 ? d.n_fft / 2 : (d.win_size - d.hop_size) / 2;
     const int Lout = mode == 0 ? d.hop_size * (F - 1) + (d.n_fft & 1) : d.hop_size * (F - 1) + d.win_size - 2 * crop;   // (odd n_fft: crop = floor(n_fft / 2) twice)
@@ -1614,6 +1634,27 @@ int amp_istft_same(const amp_mel_desc* d_in, const float* re_dev, const float* i
     if (d->hop_size <= 0 || d->hop_size > d->n_fft || ((d->win_size - d->hop_size) & 1) || B <= 0 || F <= 0) { set_error("amp_istft_same: hop=%d B=%d F=%d", d->hop_size, B, F); return AMP_ERR_INVALID; }
     hipError_t e = launch_istft(*d, 1, re_dev, im_dev, B, F, window_dev, envelope_dev, frames_ws_dev, wav_dev, (hipStream_t)stream);
     if (e != hipSuccess) { set_error("amp_istft_same: %s", hipGetErrorString(e)); return AMP_ERR_HIP; }
+    return AMP_OK;
+}
+
+int amp_istft_same_polar(const amp_mel_desc* d_in, const float* head_dev, long long head_batch_stride, int B, int F, float mag_clip,
+                         const float* window_dev, const float* envelope_dev, float* frames_ws_dev, float* wav_dev, void* stream) {
+    amp_mel_desc dn;
+    if (!mel_desc_in(d_in, &dn, "amp_istft_same_polar")) return AMP_ERR_INVALID;
+    const amp_mel_desc* d = &dn;
+    if (!head_dev || !window_dev || !envelope_dev || !frames_ws_dev || !wav_dev) { set_error("amp_istft_same_polar: null argument"); return AMP_ERR_INVALID; }
+    if (!mel_nfft_check("amp_istft_same_polar", d->n_fft) || d->win_size != d->n_fft) {
+        if (d->win_size != d->n_fft && mel_nfft_supported(d->n_fft)) set_error("amp_istft_same_polar: n_fft=%d must equal win_size=%d", d->n_fft, d->win_size);
+        return AMP_ERR_INVALID;
+    }
+    if (d->hop_size <= 0 || d->hop_size > d->n_fft || ((d->win_size - d->hop_size) & 1) || B <= 0 || F <= 0) { set_error("amp_istft_same_polar: hop=%d B=%d F=%d", d->hop_size, B, F); return AMP_ERR_INVALID; }
+    const long long rows = 2LL * (d->n_fft / 2 + 1);
+    if (head_batch_stride == 0) head_batch_stride = rows * F;
+    if (head_batch_stride < rows * F) { set_error("amp_istft_same_polar: batch stride %lld < (n_fft + 2) * F", head_batch_stride); return AMP_ERR_INVALID; }
+    if (!(mag_clip > 0.f)) { set_error("amp_istft_same_polar: mag_clip must be positive (got %g)", (double)mag_clip); return AMP_ERR_INVALID; }
+    hipError_t e = launch_istft(*d, 1, head_dev, head_dev, B, F, window_dev, envelope_dev, frames_ws_dev, wav_dev, (hipStream_t)stream,
+                                head_batch_stride, mag_clip);
+    if (e != hipSuccess) { set_error("amp_istft_same_polar: %s", hipGetErrorString(e)); return AMP_ERR_HIP; }
     return AMP_OK;
 }
 

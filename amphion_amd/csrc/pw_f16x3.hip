@@ -1,0 +1,405 @@
+// Pointwise (1 x 1) GEMM on channel-first activations for the Vocos backbone and head (models/codec/amphion_codec/vocos.py:
+// ConvNeXtBlock.pwconv1 / pwconv2 :511-526, ISTFTHead.out :346) -- nn.Linear applied along the channel axis of [B, C, T]:
+//     Y[b] = epi( W * X[b] + bias ),   W [Cout, Cin] as nn.Linear.weight stores it
+// with the epilogue chosen at compile time:
+//     AMP_PW_BIAS        y = Wx + b
+//     AMP_PW_BIAS_GELU   y = gelu_erf(Wx + b)                 (nn.GELU(), exact erf form)
+//     AMP_PW_SCALE_RES   y = res + gamma (.) (Wx + b)         (layer scale + residual; y may alias res)
+//
+// Arithmetic: the f16x3 scheme of conv_f16x3.hip -- weights pre-split on the host into hi / lo f16 planes after a per-matrix
+// 2^s scale, activations scaled x16 and split while staged, three v_mfma_f32_32x32x16_f16 per product term (Whi Xhi + Whi Xlo +
+// Wlo Xhi) into f32 accumulators, the scale undone in the epilogue, the range flag raised when a staged operand leaves the f16 range.
+//
+// Tiling.  The contraction is K = Cin (384 .. 4096), there is no halo: a K step stages 64 channels (4 MFMA k-extents), one barrier per
+// step.  Four waves as 2 x 2, each wave MI x NI 32 x 32 accumulator tiles: the 128 x 128 tile (MI = NI = 2: 64 accumulator VGPRs,
+// 12 MFMAs per 8 fragment reads per k-extent) for grids that give every CU two workgroups, the 64 x 64 tile (MI = NI = 1) for
+// single utterances, where T ~ 250 frames leaves two column tiles per item and the row tiles have to supply the workgroups.
+//   - A (weights): packed on the host in MFMA fragment order [row block][k16][plane][lane] x 16 B and read straight from L2 into
+//     VGPRs -- one 16-B load per lane per fragment, re-loaded for the next step right after its last use.
+//   - B (activations): T is the contiguous axis, so the operand is transposed while staged: a staging item is (column, channel quad),
+//     four coalesced row loads, split into hi / lo and written to LDS as [plane][channel octet][column][8 x f16]; a lane's B fragment
+//     is then one ds_read_b128.  Two LDS buffers: the loads of step s + 1 fly under the MFMAs of step s.
+// Deterministic (each output is one workgroup's full-K sum), no split-K, no atomics except the range flag.
+#include <algorithm>
+#include <memory>
+
+#include "amp_internal.h"
+#include "gelu_erf.h"
+
+namespace amp {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+union PwFrag {
+    uint4 u;
+    f16x8 h;
+};
+
+constexpr int PW_KS = 4;            // MFMA k-extents (16 channels each) per K step
+constexpr int PW_KC = 16 * PW_KS;   // channels per K step
+constexpr int PW_MROWS = 128;       // packed rows are padded to this (the larger tile's height)
+
+struct PwArgs {
+    const float* x;       // [B, Cin, T] with batch stride xbs
+    long long xbs;
+    const uint4* wp;      // packed hi / lo fragments, see amp_pw_create
+    const float* bias;    // [Cout]
+    const float* gamma;   // [Cout] (SCALE_RES)
+    const float* res;     // [B, Cout, T] (SCALE_RES; may alias y)
+    float* y;             // [B, Cout, T]
+    int Cin, Cout, T;
+    int nsteps;           // K steps of PW_KC channels
+    int nc16;             // packed k-extents per row block = nsteps * PW_KS
+    int tiles_per_item;   // ceil(T / TN)
+    float inv_scale;      // 1 / (16 * 2^s)
+    unsigned* range_flag;
+};
+
+#define AMP_PW_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
+
+template <int EPI, int MI, int NI>
+__global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
+    constexpr int TN = 64 * NI;                 // columns per workgroup
+    constexpr int NST = (4 * PW_KS * TN) / 256; // staging items (column x channel quad) per thread
+    constexpr int BUF = 2 * 2 * PW_KS * TN;     // uint4 per LDS buffer: [plane][octet][TN]
+    constexpr int PLANE = 2 * PW_KS * TN;       // uint4 per plane
+    extern __shared__ __attribute__((aligned(16))) uint4 pw_smem[];   // [2][BUF]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int hi = lane >> 5, l31 = lane & 31;
+    const int bx = blockIdx.x;
+    const int item = bx / a.tiles_per_item;
+    const int q0 = (bx - item * a.tiles_per_item) * TN;
+    const int mb0 = blockIdx.y * (2 * MI) + wm * MI;     // first 32-row block of this wave
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int t = 0; t < NI; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][t][r] = 0.f;
+
+    const float* xb = a.x + (size_t)item * (size_t)a.xbs;
+    const int T = a.T, Cin = a.Cin;
+    float range_max = 0.f;
+    float xs[NST][4];
+    // staging item i = wave * 64 + 256 * it + lane: channel quad (i / TN, wave-uniform: TN is a multiple of 64) x column (i % TN)
+    auto stage_load = [&](int step) {
+#pragma unroll
+        for (int it = 0; it < NST; ++it) {
+            const int ibase = wave * 64 + 256 * it;
+            const int qd = ibase / TN;
+            const int col = ibase - qd * TN + lane;
+            int t = q0 + col;
+            t = t > T - 1 ? T - 1 : t;
+            const int ch0 = step * PW_KC + 4 * qd;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                int ch = ch0 + e;
+                ch = ch > Cin - 1 ? Cin - 1 : ch;
+                xs[it][e] = xb[(size_t)ch * T + t];
+            }
+        }
+    };
+    auto stage_store = [&](int step, int buf) {
+        uint2* dst = reinterpret_cast<uint2*>(pw_smem + buf * BUF);
+#pragma unroll
+        for (int it = 0; it < NST; ++it) {
+            const int ibase = wave * 64 + 256 * it;
+            const int qd = ibase / TN;
+            const int col = ibase - qd * TN + lane;
+            const bool tok = q0 + col < T;
+            const int ch0 = step * PW_KC + 4 * qd;
+            uint2 fh, fl;
+            stage4_f16((tok && ch0 + 0 < Cin) ? xs[it][0] : 0.f, (tok && ch0 + 1 < Cin) ? xs[it][1] : 0.f,
+                       (tok && ch0 + 2 < Cin) ? xs[it][2] : 0.f, (tok && ch0 + 3 < Cin) ? xs[it][3] : 0.f, 16.f, 16.f, range_max, fh, fl);
+            const int o2 = (((qd >> 1) * TN + col) << 1) + (qd & 1);   // uint2 index inside a plane
+            dst[o2] = fh;
+            dst[2 * PLANE + o2] = fl;
+        }
+    };
+
+    // A fragments of one K step: [k-extent][row block][plane]; entry (mb, c16, plane) of the pack at ((mb * nc16 + c16) * 2 + plane) * 64
+    const uint4* wa = a.wp + (size_t)mb0 * a.nc16 * 128 + lane;
+    const size_t mbs = (size_t)a.nc16 * 128;           // uint4 per row block
+    PwFrag ah[PW_KS][MI], al[PW_KS][MI];
+#pragma unroll
+    for (int h = 0; h < PW_KS; ++h)
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            ah[h][i].u = wa[i * mbs + h * 128];
+            al[h][i].u = wa[i * mbs + h * 128 + 64];
+        }
+    stage_load(0);
+    AMP_PW_PIN_VMEM();
+    stage_store(0, 0);
+    __syncthreads();
+
+    const int rd0 = hi * TN + wn * (32 * NI) + l31;
+    auto step = [&](const int s, const bool more) __attribute__((always_inline)) {
+        if (more) {
+            stage_load(s + 1);
+            AMP_PW_PIN_VMEM();
+        }
+        wa += PW_KS * 128;
+        const uint4* base = pw_smem + (s & 1) * BUF + rd0;
+#pragma unroll
+        for (int h = 0; h < PW_KS; ++h) {
+            const uint4* bg = base + (2 * h) * TN;
+            PwFrag bh[NI], bl[NI];
+#pragma unroll
+            for (int t = 0; t < NI; ++t) {
+                bh[t].u = bg[32 * t];
+                bl[t].u = bg[PLANE + 32 * t];
+            }
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[h][i].h, bh[t].h, acc[i][t], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[h][i].h, bl[t].h, acc[i][t], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[h][i].h, bh[t].h, acc[i][t], 0, 0, 0);
+            if (more) {
+#pragma unroll
+                for (int i = 0; i < MI; ++i) {
+                    ah[h][i].u = wa[i * mbs + h * 128];
+                    al[h][i].u = wa[i * mbs + h * 128 + 64];
+                }
+                AMP_PW_PIN_VMEM();
+            }
+        }
+        if (more) stage_store(s + 1, (s + 1) & 1);
+        __syncthreads();
+    };
+    const int nsteps = a.nsteps;
+    for (int s = 0; s + 1 < nsteps; ++s) step(s, true);
+    step(nsteps - 1, false);
+
+    if (a.range_flag && __any(range_max > 65504.f) && lane == 0) atomicOr(a.range_flag, 1u);
+
+    // ---- epilogue: lane (hi, l31), register r of tile (i, t) holds row (r & 3) + 8 (r >> 2) + 4 hi, column 32 t + l31 ----
+    const size_t ybase = (size_t)item * a.Cout * T;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = (mb0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (m >= a.Cout) continue;
+            const float bv = a.bias[m];
+            const float gv = EPI == AMP_PW_SCALE_RES ? a.gamma[m] : 0.f;
+            const size_t row = ybase + (size_t)m * T;
+#pragma unroll
+            for (int t = 0; t < NI; ++t) {
+                const int q = q0 + wn * (32 * NI) + 32 * t + l31;
+                if (q >= T) continue;
+                float v = acc[i][t][r] * a.inv_scale + bv;
+                if (EPI == AMP_PW_BIAS_GELU) v = gelu_erf(v);
+                if (EPI == AMP_PW_SCALE_RES) v = a.res[row + q] + gv * v;
+                a.y[row + q] = v;
+            }
+        }
+    }
+}
+
+template <int EPI, int MI, int NI>
+static hipError_t pw_launch_one(const PwArgs& a, int B, hipStream_t stream) {
+    constexpr int TN = 64 * NI;
+    const size_t lds = (size_t)2 * 2 * 2 * PW_KS * TN * sizeof(uint4);
+    if (hipError_t e = ensure_dynamic_lds<&pw_f16x3_kernel<EPI, MI, NI>>(lds); e != hipSuccess) return e;
+    const dim3 grid((unsigned)(B * a.tiles_per_item), (unsigned)((a.Cout + 64 * MI - 1) / (64 * MI)));
+    note_kernel("pw_f16x3_kernel", EPI, MI, NI);
+    if (manifest_on()) {
+        const double gf = 2.0 * a.Cout * (double)a.Cin * a.T * B / 1e9;
+        const double mb = 4.0 * B * ((double)a.Cin * a.T + (double)a.Cout * a.T * (EPI == AMP_PW_SCALE_RES ? 2 : 1)) / 1e6;
+        note_work((unsigned long long)grid.x * grid.y, gf, mb, "pw %d->%d epi=%d T=%d B=%d grid=%ux%u", a.Cin, a.Cout, EPI, a.T, B, grid.x, grid.y);
+    }
+    hipLaunchKernelGGL((pw_f16x3_kernel<EPI, MI, NI>), grid, dim3(256), lds, stream, a);
+    return hipGetLastError();
+}
+
+// the large tile wherever it still gives every CU two workgroups; the small one otherwise (single utterances)
+template <int EPI>
+static hipError_t pw_launch(PwArgs a, int B, hipStream_t stream) {
+    const long long big = (long long)B * ((a.T + 127) / 128) * ((a.Cout + 127) / 128);
+    if (big >= 512) {
+        a.tiles_per_item = (a.T + 127) / 128;
+        return pw_launch_one<EPI, 2, 2>(a, B, stream);
+    }
+    a.tiles_per_item = (a.T + 63) / 64;
+    return pw_launch_one<EPI, 1, 1>(a, B, stream);
+}
+
+// exact-fp32 mode: the k = 1 conv (conv_mfma.hip) writes Wx + b, this applies the rest of the epilogue in place
+__global__ __launch_bounds__(256) void pw_epilogue_kernel(float* __restrict__ y, const float* __restrict__ res, const float* __restrict__ gamma,
+                                                          int epi, int C, int T, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = y[i];
+    if (epi == AMP_PW_BIAS_GELU) v = gelu_erf(v);
+    else {
+        const int c = (int)((i / (size_t)T) % (size_t)C);
+        v = res[i] + gamma[c] * v;
+    }
+    out[i] = v;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+struct amp_pw {
+    int cin = 0, cout = 0;
+    int precision = PREC_F16X3;
+    int nsteps = 0;
+    float inv_scale = 1.f;
+    uint4* wp_dev = nullptr;     // f16x3: packed fragments
+    float* bias_dev = nullptr;   // [cout] (zeros when the Linear has no bias)
+    amp_conv* conv = nullptr;    // exact-fp32 mode: the k = 1 conv
+    ~amp_pw() {
+        if (wp_dev) (void)hipFree(wp_dev);
+        if (bias_dev) (void)hipFree(bias_dev);
+        if (conv) amp_conv_destroy(conv);
+    }
+};
+
+#define PW_HIP(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e__ = (expr);                                                                       \
+        if (e__ != hipSuccess) {                                                                       \
+            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);     \
+            return AMP_ERR_HIP;                                                                        \
+        }                                                                                              \
+    } while (0)
+
+extern "C" {
+
+int amp_pw_create(int cin, int cout, const float* weight_host, const float* bias_host, amp_pw** out) {
+    if (!out || !weight_host || cin <= 0 || cout <= 0) { set_error("amp_pw_create: bad argument cin=%d cout=%d", cin, cout); return AMP_ERR_INVALID; }
+    *out = nullptr;
+    std::unique_ptr<amp_pw> p(new amp_pw);
+    p->cin = cin;
+    p->cout = cout;
+    p->precision = amp_get_precision();
+    std::vector<float> bias((size_t)cout, 0.f);
+    if (bias_host) std::copy(bias_host, bias_host + cout, bias.begin());
+    if (p->precision == PREC_F32) {
+        // [cout, cin] is the Conv1d weight [cout, cin, 1]
+        if (int rc = amp_conv_create(0, cin, cout, 1, 1, 1, 0, weight_host, bias.data(), &p->conv); rc != AMP_OK) return rc;
+    } else {
+        // per-matrix 2^s: max|w| in (2^12, 2^13], as conv_build does
+        float wmax = 0.f;
+        const size_t nw = (size_t)cin * cout;
+        for (size_t i = 0; i < nw; ++i) wmax = fmaxf(wmax, fabsf(weight_host[i]));
+        if (!(wmax < 1e30f)) { set_error("amp_pw_create: non-finite weight"); return AMP_ERR_INVALID; }
+        int e2 = 0;
+        if (wmax > 0.f) { (void)frexpf(wmax, &e2); if (ldexpf(1.f, e2 - 1) == wmax) e2 -= 1; }
+        const float wscale = wmax > 0.f ? ldexpf(1.f, 13 - e2) : 1.f;
+        p->inv_scale = 1.f / (16.f * wscale);
+        p->nsteps = (cin + PW_KC - 1) / PW_KC;
+        const int nc16 = p->nsteps * PW_KS;
+        const int nmb = (cout + PW_MROWS - 1) / PW_MROWS * (PW_MROWS / 32);
+        // [row block][k16][plane hi | lo][lane][8 x f16]: lane l holds row 32 mb + (l & 31), channels 16 c16 + 8 (l >> 5) + 0..7
+        const size_t n16 = (size_t)nmb * nc16 * 2 * 64 * 8;
+        std::vector<_Float16> wp(n16, (_Float16)0.f);
+        for (int mb = 0; mb < nmb; ++mb)
+            for (int c16 = 0; c16 < nc16; ++c16)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int m = mb * 32 + (lane & 31);
+                    for (int e = 0; e < 8; ++e) {
+                        const int i = c16 * 16 + 8 * (lane >> 5) + e;
+                        const float v = (m < cout && i < cin) ? weight_host[(size_t)m * cin + i] * wscale : 0.f;
+                        const _Float16 h = (_Float16)v;
+                        const _Float16 l = (_Float16)(v - (float)h);
+                        const size_t ent = ((size_t)mb * nc16 + c16) * 2;
+                        wp[((ent + 0) * 64 + lane) * 8 + e] = h;
+                        wp[((ent + 1) * 64 + lane) * 8 + e] = l;
+                    }
+                }
+        PW_HIP(hipMalloc((void**)&p->wp_dev, n16 * sizeof(_Float16)));
+        PW_HIP(hipMemcpy(p->wp_dev, wp.data(), n16 * sizeof(_Float16), hipMemcpyHostToDevice));
+        PW_HIP(hipMalloc((void**)&p->bias_dev, (size_t)cout * sizeof(float)));
+        PW_HIP(hipMemcpy(p->bias_dev, bias.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *out = p.release();
+    return AMP_OK;
+}
+
+int amp_pw_precision(const amp_pw* p) { return p ? p->precision : -1; }
+
+int amp_pw_forward(const amp_pw* p, const float* x_dev, long long x_batch_stride, int B, int T, int epilogue, const float* gamma_dev,
+                   const float* res_dev, float* y_dev, void* stream_) {
+    if (!p || !x_dev || !y_dev || B <= 0 || T <= 0 || B > 65535) { set_error("amp_pw_forward: bad argument (B=%d T=%d)", B, T); return AMP_ERR_INVALID; }
+    if (epilogue != AMP_PW_BIAS && epilogue != AMP_PW_BIAS_GELU && epilogue != AMP_PW_SCALE_RES) {
+        set_error("amp_pw_forward: unknown epilogue %d", epilogue);
+        return AMP_ERR_INVALID;
+    }
+    if (epilogue == AMP_PW_SCALE_RES && (!gamma_dev || !res_dev)) { set_error("amp_pw_forward: AMP_PW_SCALE_RES needs gamma and res"); return AMP_ERR_INVALID; }
+    if (x_batch_stride == 0) x_batch_stride = (long long)p->cin * T;
+    if (x_batch_stride < (long long)p->cin * T) { set_error("amp_pw_forward: batch stride %lld < cin*T", x_batch_stride); return AMP_ERR_INVALID; }
+    const size_t xspan = (size_t)(B - 1) * (size_t)x_batch_stride + (size_t)p->cin * T;
+    const float* ylo = y_dev;
+    const float* yhi = y_dev + (size_t)B * p->cout * T;
+    if (x_dev < yhi && ylo < x_dev + xspan) { set_error("amp_pw_forward: x and y must not overlap"); return AMP_ERR_INVALID; }
+    if (epilogue == AMP_PW_SCALE_RES && res_dev != y_dev) {
+        const float* rhi = res_dev + (size_t)B * p->cout * T;
+        if (res_dev < yhi && ylo < rhi) { set_error("amp_pw_forward: res must be y or not overlap it"); return AMP_ERR_INVALID; }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    if (p->precision == PREC_F32) {
+        const size_t n = (size_t)B * p->cout * T;
+        // y aliasing res: Wx + b goes to a stream-ordered temporary of this call (allocated and freed on `stream`, so a handle holds
+        // no mutable state and two streams may share it)
+        float* tmp = nullptr;
+        if (epilogue == AMP_PW_SCALE_RES && res_dev == y_dev) PW_HIP(hipMallocAsync((void**)&tmp, n * sizeof(float), stream));
+        float* dst = tmp ? tmp : y_dev;
+        int rc = amp_conv_forward_strided(p->conv, x_dev, x_batch_stride, B, T, 1.f, nullptr, 1.f, dst, stream_);
+        if (rc == AMP_OK && epilogue != AMP_PW_BIAS) {
+            note_kernel("pw_epilogue_kernel");
+            const unsigned nb = (unsigned)((n + 255) / 256);
+            note_work(nb, 0.0, 4.0 * n * (epilogue == AMP_PW_SCALE_RES ? 3 : 2) / 1e6, "pw epilogue %d C=%d T=%d B=%d", epilogue, p->cout, T, B);
+            hipLaunchKernelGGL(pw_epilogue_kernel, dim3(nb), dim3(256), 0, stream, dst, res_dev, gamma_dev, epilogue, p->cout, T, n, y_dev);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_error("amp_pw_forward: %s", hipGetErrorString(e)); rc = AMP_ERR_HIP; }
+        }
+        if (tmp) {
+            const hipError_t e = hipFreeAsync(tmp, stream);
+            if (e != hipSuccess && rc == AMP_OK) { set_error("amp_pw_forward: hipFreeAsync: %s", hipGetErrorString(e)); rc = AMP_ERR_HIP; }
+        }
+        return rc;
+    }
+    PwArgs a{};
+    a.x = x_dev;
+    a.xbs = x_batch_stride;
+    a.wp = p->wp_dev;
+    a.bias = p->bias_dev;
+    a.gamma = gamma_dev;
+    a.res = res_dev;
+    a.y = y_dev;
+    a.Cin = p->cin;
+    a.Cout = p->cout;
+    a.T = T;
+    a.nsteps = p->nsteps;
+    a.nc16 = p->nsteps * PW_KS;
+    a.inv_scale = p->inv_scale;
+    a.range_flag = range_flag_for_current_device();
+    hipError_t e;
+    if (epilogue == AMP_PW_BIAS) e = pw_launch<AMP_PW_BIAS>(a, B, stream);
+    else if (epilogue == AMP_PW_BIAS_GELU) e = pw_launch<AMP_PW_BIAS_GELU>(a, B, stream);
+    else e = pw_launch<AMP_PW_SCALE_RES>(a, B, stream);
+    if (e != hipSuccess) { set_error("amp_pw_forward: %s", hipGetErrorString(e)); return AMP_ERR_HIP; }
+    return AMP_OK;
+}
+
+void amp_pw_destroy(amp_pw* p) { delete p; }
+
+}  // extern "C"

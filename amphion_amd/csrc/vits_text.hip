@@ -6,6 +6,7 @@
 // latency-bound; the kernels are written for clarity (one thread per output, coalesced along time), the dense
 // convolutions between them run on conv_f16x3.hip.  Layout [B, C, T], fp32.
 #include "amp_internal.h"
+#include "gelu_erf.h"
 
 #include <atomic>
 #include <mutex>
@@ -18,15 +19,7 @@ namespace amp {
 // a run-time `if (post)`, did not; hipcc's __fmul_rn is a plain multiply and does not stop it).  Contraction is switched off inside
 // these helpers and the fused operations are written out, so every kernel that normalises rounds alike and the fused forms can be
 // tested bit for bit; the opaque move keeps a CALLER from contracting across the return value.
-__device__ __forceinline__ float fp_opaque(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ float gelu_erf(float v) {
-#pragma clang fp contract(off)
-    const float e = 1.0f + fp_opaque(erff(v * 0.70710678118654752f));
-    return fp_opaque((0.5f * v) * e);
-}
+// (fp_opaque and gelu_erf: gelu_erf.h)
 __device__ __forceinline__ float ln_sq_acc(float part, float d, bool on) {
     const float dd = on ? d : 0.f;
     return fmaf(dd, dd, part);
@@ -940,8 +933,9 @@ static int layer_norm_run(const char* who, const float* x_dev, const float* res_
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, x_dev,
                            res_dev, gamma_dev, beta_dev, post_dev, lens_dev, nullptr, nullptr, 1, y_dev, C, T, eps, gelu);
     } else {
-        VT_CHECK(K == 3 && dil > 0 && C <= LN_DW_MAXC, "%s: the fused depthwise prologue covers K = 3, C <= %d (got K=%d dilation=%d C=%d): run amp_dwconv first", who, LN_DW_MAXC, K, dil, C);
-        auto kern = nc24 ? layer_norm_c_kernel<3, 24> : layer_norm_c_kernel<3, 32>;
+        VT_CHECK((K == 3 || K == 7) && dil > 0 && C <= LN_DW_MAXC, "%s: the fused depthwise prologue covers K = 3 or 7, C <= %d (got K=%d dilation=%d C=%d): run amp_dwconv first", who, LN_DW_MAXC, K, dil, C);
+        // K = 7 (ConvNeXt's dwconv, vocos.py:489-496): 16 channels per thread in registers -- 7 taps of 32 would not fit the VGPR file
+        auto kern = K == 7 ? layer_norm_c_kernel<7, 16> : nc24 ? layer_norm_c_kernel<3, 24> : layer_norm_c_kernel<3, 32>;
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, x_dev,
                            res_dev, gamma_dev, beta_dev, post_dev, lens_dev, dw_w, dw_b, dil, y_dev, C, T, eps, gelu);
     }

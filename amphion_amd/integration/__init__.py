@@ -30,11 +30,20 @@ CLASS_TARGETS = {
 }
 
 
-def _patch_classes(module, fullname):
+# Vocos (models/codec/amphion_codec/vocos.py:824-881), the vocoder of Vevo / VevoSing (models/vc/vevo/vevo_utils.py:117-118,
+# models/svc/vevosing/vevosing_utils.py:96) and of the MaskGCT codec decoder (models/codec/amphion_codec/codec.py:372-382).
+# It has its own one-shot finder: _Finder leaves sys.meta_path once the registries and the generator modules are patched,
+# whether or not a codec package is ever imported.
+CODEC_CLASS_TARGETS = {
+    "models.codec.amphion_codec.vocos": ("Vocos",),
+}
+
+
+def _patch_classes(module, fullname, targets=CLASS_TARGETS):
     import importlib
 
     ours = importlib.import_module("amphion_amd." + fullname)
-    for name in CLASS_TARGETS[fullname]:
+    for name in targets[fullname]:
         if hasattr(module, name) and hasattr(ours, name):
             setattr(module, "_reference_" + name, getattr(module, name))     # the original stays reachable
             setattr(module, name, getattr(ours, name))
@@ -86,7 +95,56 @@ class _Finder(importlib.abc.MetaPathFinder):
         return spec
 
 
+class _ClassPatchLoader(importlib.abc.Loader):
+    def __init__(self, inner):
+        self._inner = inner
+
+    def create_module(self, spec):
+        return self._inner.create_module(spec)
+
+    def exec_module(self, module):
+        self._inner.exec_module(module)
+        _patch_classes(module, module.__name__, CODEC_CLASS_TARGETS)
+
+
+class _CodecFinder(importlib.abc.MetaPathFinder):
+    """One shot per module of CODEC_CLASS_TARGETS; leaves sys.meta_path when all of them are patched."""
+
+    def __init__(self, pending):
+        self._pending = set(pending)
+        self._busy = False
+
+    def find_spec(self, fullname, path, target=None):
+        if self._busy or fullname not in self._pending:
+            return None
+        self._pending.discard(fullname)
+        self._busy = True
+        try:
+            spec = importlib.util.find_spec(fullname)
+        finally:
+            self._busy = False
+        if not self._pending:
+            sys.meta_path.remove(self)
+        if spec is None or spec.loader is None:
+            return None
+        spec.loader = _ClassPatchLoader(spec.loader)
+        return spec
+
+
+def _install_codec():
+    pending = []
+    for t in CODEC_CLASS_TARGETS:
+        m = sys.modules.get(t)
+        if m is None:
+            pending.append(t)
+        elif not getattr(m, "__amphion_amd_patched__", False):
+            _patch_classes(m, t, CODEC_CLASS_TARGETS)
+    if pending and not any(isinstance(f, _CodecFinder) for f in sys.meta_path):
+        sys.meta_path.insert(0, _CodecFinder(pending))
+
+
 def install():
+    _install_codec()
     from_loaded = [t for t in TARGETS if t in sys.modules]
     if from_loaded:
         from amphion_amd.models.vocoders.vocoder_inference import install_into_reference

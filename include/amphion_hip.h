@@ -92,7 +92,8 @@ typedef struct amp_gen amp_gen;
  * amp_conv_act_forward, amp_set_fuse_act and amp_set_wn_layer_fusion together with the kernels behind them (bit-identical forms the launch
  * policy never chose), refuses amp_set_pair_strips(1), and lets amp_mel_forward / amp_mel_backward / amp_istft_forward / amp_istft_same take
  * any n_fft in [64, 4096] (mixed-radix kernels: compile-time butterflies for the primes 2 .. 13, a run-time radix pass for larger prime factors;
- * powers of two keep their kernels). */
+ * powers of two keep their kernels); 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision /
+ * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -243,8 +244,8 @@ int amp_layer_norm_c_ragged(const float* x_dev, const float* res_dev, const floa
                             const float* post_dev, const int* lens_dev, int B, int C, int T, float eps, int gelu, float* y_dev,
                             void* stream);
 /* act(LN(dwconv(x * mask))) in one launch: DDSConv's convs_sep[i] -> norms_1[i] -> gelu (modules/flow/modules.py:63-65), the
- * depthwise taps evaluated on load in amp_dwconv's order (same bits as the two launches).  K = 3 (AMP_ERR_INVALID otherwise: run
- * amp_dwconv + amp_layer_norm_c); dw_weight [C, 1, K], dw_bias [C] or NULL; columns t >= lens[b] of y are zero; y != x. */
+ * depthwise taps evaluated on load in amp_dwconv's order (same bits as the two launches).  K = 3, or K = 7 with C <= 1024 (ConvNeXt's
+ * dwconv -> LayerNorm, vocos.py:489-496,511-518) (AMP_ERR_INVALID otherwise: run amp_dwconv + amp_layer_norm_c); dw_weight [C, 1, K], dw_bias [C] or NULL; columns t >= lens[b] of y are zero; y != x. */
 int amp_dwconv_layer_norm_c(const float* x_dev, const float* dw_weight_dev, const float* dw_bias_dev, int K, int dilation,
                             const float* gamma_dev, const float* beta_dev, const int* lens_dev, int B, int C, int T, float eps,
                             int gelu, float* y_dev, void* stream);
@@ -549,6 +550,33 @@ int amp_istft_forward(const amp_mel_desc* d, const float* mag_dev, const float* 
  * window envelope.  envelope_dev [hop*(F-1) + win] = overlap-added window^2 (uncropped); needs win_size == n_fft. */
 int amp_istft_same(const amp_mel_desc* d, const float* re_dev, const float* im_dev, int B, int F, const float* window_dev,
                    const float* envelope_dev, float* frames_ws_dev, float* wav_dev, void* stream);
+
+/* Vocos's ISTFT head (vocos.py:346-359 + ISTFT "same", :84-167) in one call: reads the head Linear's output
+ * head [B, n_fft + 2, F] (batch stride head_batch_stride elements, 0 = dense) in place -- rows [0, n_fft/2+1) are log-magnitude,
+ * rows [n_fft/2+1, n_fft+2) phase -- forms min(exp(m), mag_clip) * (cos p, sin p) while loading each frame (exp overflowing to
+ * inf clips to mag_clip; full-range sincos) and then runs amp_istft_same's overlap-add and envelope division -> wav [B, F * hop].
+ * Same window / envelope / scratch contract as amp_istft_same. */
+int amp_istft_same_polar(const amp_mel_desc* d, const float* head_dev, long long head_batch_stride, int B, int F, float mag_clip,
+                         const float* window_dev, const float* envelope_dev, float* frames_ws_dev, float* wav_dev, void* stream);
+
+/* ---- pointwise GEMM (csrc/pw_f16x3.hip): nn.Linear along the channel axis of [B, C, T] activations, Vocos's
+ * ConvNeXtBlock.pwconv1 / pwconv2 and ISTFTHead.out (vocos.py:511-526,346).  y[b] = epi(W x[b] + bias) with
+ *   AMP_PW_BIAS        y = Wx + b
+ *   AMP_PW_BIAS_GELU   y = gelu(Wx + b)                (exact erf GELU, nn.GELU())
+ *   AMP_PW_SCALE_RES   y = res + gamma (.) (Wx + b)    (per-row gamma [cout]; res [B, cout, T] may alias y)
+ * weight_host [cout, cin] as nn.Linear.weight stores it, bias_host [cout] or NULL.  The arithmetic is fixed when the handle is
+ * created (amp_set_precision): f16x3 runs the split-f16 MFMA kernel (its operand range is guarded: amp_range_check reports
+ * AMP_ERR_RANGE); AMP_PRECISION_F32 runs the exact-f32 k = 1 conv and one element-wise epilogue.  x [B, cin, T] with batch stride
+ * x_batch_stride elements (0 = dense), y [B, cout, T] dense; x must not overlap y.  Deterministic.  A handle holds no mutable
+ * state: several streams may use one (the fp32 route with y == res takes a stream-ordered temporary, hipMallocAsync / hipFreeAsync). ---- */
+typedef struct amp_pw amp_pw;
+typedef enum amp_pw_epilogue { AMP_PW_BIAS = 0, AMP_PW_BIAS_GELU = 1, AMP_PW_SCALE_RES = 2 } amp_pw_epilogue;
+int amp_pw_create(int cin, int cout, const float* weight_host, const float* bias_host, amp_pw** out);
+int amp_pw_forward(const amp_pw* p, const float* x_dev, long long x_batch_stride, int B, int T, int epilogue,
+                   const float* gamma_dev, const float* res_dev, float* y_dev, void* stream);
+/* the precision the handle was created with (AMP_PRECISION_*), -1 for NULL */
+int amp_pw_precision(const amp_pw* p);
+void amp_pw_destroy(amp_pw* p);
 
 #ifdef __cplusplus
 }
