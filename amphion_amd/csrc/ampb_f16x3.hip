@@ -43,7 +43,7 @@
 //
 // Compiled once per tap count:  -DAMP_KT=<3|5|7|11>.
 #include "act1d_math.h"
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #ifndef AMP_KT
 #error "compile with -DAMP_KT=<taps>"
@@ -51,16 +51,6 @@
 #include <type_traits>
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union FragQ {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 // P layout: run column c (0 .. 63) of a lane lives in v[AMP_PT(c)][AMP_PR(c)]
 #define AMP_PT(c) ((c) >> 4)
@@ -200,9 +190,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void ampb_f16x3_kernel(const AmpbA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int h = lane >> 5, m = lane & 31;
-    const int nbx = gridDim.x;  // XCD-contiguous tile runs, see conv_f16x3.hip (ragged batches keep the dispatch order)
-    int bx = ((nbx & 7) == 0 && !a.lens) ? (int)(blockIdx.x & 7) * (nbx >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (a.rev) bx = nbx - 1 - bx;
+    const int nbx = gridDim.x;  // XCD-contiguous tile runs, tile_order() in f16x3_device.h
+    int bx = tile_order(blockIdx.x, nbx, a.lens != nullptr, a.rev);
     const int item = bx / a.tiles_per_item;
     const int tile = bx - item * a.tiles_per_item;
     const int T = a.T;
@@ -256,7 +245,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void ampb_f16x3_kernel(const AmpbA
     // exactly what it holds as the A operand of the plain one
     constexpr size_t MBS = (size_t)NCH * (KT * 128);
     constexpr int NA = RING > 0 ? RING : KT;
-    FragQ w_h[NA], w_l[NA];
+    Frag w_h[NA], w_l[NA];
 
     float range_max = 0.f;       // largest |staged operand| (x16 applied): beyond 65504 it left the f16 range (a.range_flag)
     const int e8 = lane & 7, o4 = (lane >> 3) & 3;
@@ -452,7 +441,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void ampb_f16x3_kernel(const AmpbA
                     const uint4* bg = base + g * d;
 #pragma unroll
                     for (int th = 0; th < 2; ++th) {      // the tap's x fragments in two halves (16 registers instead of 32)
-                        FragQ xh[2], xl[2];
+                        Frag xh[2], xl[2];
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
                             xh[t].u = bg[16 * (th * 2 + t)];

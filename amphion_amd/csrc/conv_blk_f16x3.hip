@@ -14,23 +14,13 @@
 // that of conv_f16x3.hip: the results are bit-identical (tests/test_gpu_f16x3_kernels.py).
 //
 // Compiled once per tap count:  -DAMP_KT=<2|3|7|11>.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #ifndef AMP_KT
 #error "compile with -DAMP_KT=<taps>"
 #endif
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union FragB {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 // 4 / WN waves along M, WN along the columns, MI = 2 row blocks per wave: 256 / WN rows x WN * 32 * NI columns per workgroup.
 // WN = 1: 256-row groups (the C = 256 stage, the transposed convs' polyphase rows); round 4: WN = 2 for convs with 128 rows -- BigVGAN's
@@ -62,9 +52,8 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5, l31 = lane & 31;
-    const int nbx = gridDim.x;   // XCD-contiguous tile runs, see conv_f16x3.hip
-    int bx = ((nbx & 7) == 0 && !a.lens) ? (int)(blockIdx.x & 7) * (nbx >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (a.rev) bx = nbx - 1 - bx;   // descending tile order: start where the previous launch stopped writing (ConvArgs::rev)
+    const int nbx = gridDim.x;   // XCD-contiguous tile runs, descending when a.rev: tile_order() in f16x3_device.h
+    int bx = tile_order(blockIdx.x, nbx, a.lens != nullptr, a.rev);
     int rg = blockIdx.y;         // 256-row group
     if (a.row_groups > 0) { rg = bx % a.row_groups; bx /= a.row_groups; }   // row group fastest, see ConvArgs
     const int item = bx / a.tiles_per_item;
@@ -209,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
     const size_t mbs = (size_t)a.nchunks * (KT * 128);   // uint4 per row block
     const uint4* wa = static_cast<const uint4*>(a.wp) + (size_t)mb0 * mbs + lane;
     constexpr int NA = RING > 0 ? RING : VT;             // A-fragment register sets held per row block
-    FragB a_h[MI][NA], a_l[MI][NA];
+    Frag a_h[MI][NA], a_l[MI][NA];
 
     const int rd0 = hi * S + wnc + l31 + a.halo_left + a.off0;
     const int dstep = a.dstep;
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
                 constexpr int NB = NI / BH;
 #pragma unroll
                 for (int th = 0; th < BH; ++th) {
-                    FragB bh[NB], bl[NB];
+                    Frag bh[NB], bl[NB];
 #pragma unroll
                     for (int t = 0; t < NB; ++t) {
                         bh[t].u = bg[32 * (th * NB + t)];
@@ -255,15 +244,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
                     }
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bh[t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bl[t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[mi][v].h, bh[t].h, acc[mi][th * NB + t], 0, 0, 0);
+                        mfma3<NB>(acc[mi] + th * NB, a_h[mi][v], a_l[mi][v], bh, bl);
                         if (th == BH - 1) {
                             a_h[mi][v].u = wa[mi * mbs + vn * 128];
                             a_l[mi][v].u = wa[mi * mbs + vn * 128 + 64];

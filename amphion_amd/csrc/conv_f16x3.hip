@@ -23,7 +23,7 @@
 //     all 64 banks).  leaky_relu-on-load, zero padding and the f32 -> hi/lo split happen while staging.
 //
 // This file is compiled once per tap count:  -DAMP_KT=<1|2|3|5|7|11>.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #ifndef AMP_KT
 #error "compile with -DAMP_KT=<taps>"
@@ -31,19 +31,7 @@
 
 namespace amp {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-union Frag {
-    uint4 u;
-    f16x8 h;
-};
-
-// VMEM and MFMA may not cross (VALU, SALU, DS may): pins where the global loads are issued relative to
-// the MFMA blocks and their issue ORDER, on which the
-// counted s_waitcnt vmcnt(N) the compiler derives depends (loads return in order).
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 template <int KT, int WM, int WN, int NI, int HALO>
 __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {

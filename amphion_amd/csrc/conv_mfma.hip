@@ -13,15 +13,13 @@
 //   - fp32 MFMA is bit-for-bit an fmaf chain, so parity with the fp32 reference is at rounding level.
 //
 // This file is compiled once per tap count:  -DAMP_KT=<1|2|3|5|7|11>.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #ifndef AMP_KT
 #error "compile with -DAMP_KT=<taps>"
 #endif
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int KT, int WM, int WN, int NI, int HALO>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
@@ -35,13 +33,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int hi = lane >> 5, l31 = lane & 31;
-    // Workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), each with its own
-    // L2: hand every XCD a contiguous run of tiles, so the halo columns two neighbouring tiles share
-    // are fetched into ONE L2 instead of two.
     const int nbx = gridDim.x;
-    // (ragged batches keep the dispatch order: with utterances of different lengths a contiguous run per XCD would hand
-    // one XCD the long utterances and another only tiles that exit at once -- measured 43.8 vs 48.7 ms padded, visit AD)
-    const int bx = ((nbx & 7) == 0 && !a.lens) ? (int)(blockIdx.x & 7) * (nbx >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int bx = tile_order(blockIdx.x, nbx, a.lens != nullptr, 0);   // (this kernel has no descending order)
     const int item = bx / a.tiles_per_item;
     const int tile = bx - item * a.tiles_per_item;
     const int q0 = tile * NT;
@@ -204,7 +197,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
     // ---- epilogue: MRF mean, activation-on-store, (polyphase) scatter ----
     const float slope_out = a.slope_out;
     if (fast) {
-        const float scale = a.mode == 2 ? 1.f / a.div : 1.f;
         float* yp = a.y + wave_base;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -213,7 +205,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
             for (int t = 0; t < NI; ++t) {
                 float v = acc[t][r];
                 if (a.mode == 2) v = v / a.div;
-                (void)scale;
                 v = v > 0.f ? v : v * slope_out;
                 if (a.tanh_out) v = tanhf(v);
                 yr_[lane_off + 32 * t] = v;

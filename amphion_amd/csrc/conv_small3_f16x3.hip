@@ -25,7 +25,7 @@ static hipError_t launch_small3_one(const ConvSmall3Args& p, hipStream_t stream)
         const int S = j == 0 ? 32 * NI0 + HALO0 : 64;
         const int AR = kt <= 3 ? 4 : 2;                    // ARing<KT>::n
         const size_t l = (size_t)((p.a[j].nchunks + AR - 1) / AR * AR) * 4 * S * sizeof(uint4);
-        if (p.a[j].nchunks > kSmallMaxChunks || l > kSmallMaxLds || p.a[j].wd > S) return hipErrorInvalidValue;
+        if (p.a[j].nchunks > kSmallConvMaxChunks || l > kSmallMaxLds || p.a[j].wd > S) return hipErrorInvalidValue;
         lds = l > lds ? l : lds;
     }
     if (hipError_t e = ensure_dynamic_lds<&conv_small3_kernel<NI0, HALO0>>(kSmallMaxLds); e != hipSuccess) return e;

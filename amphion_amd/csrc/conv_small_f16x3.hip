@@ -48,7 +48,7 @@ static hipError_t launch_small_one(const ConvArgs& a, hipStream_t stream) {
     constexpr int S = 32 * NI + HALO;
     constexpr int AR = ARing<KT>::n;
     const size_t lds = (size_t)((a.nchunks + AR - 1) / AR * AR) * 4 * S * sizeof(uint4);
-    if (a.nchunks > kSmallMaxChunks || lds > kSmallMaxLds || a.wd > S) return hipErrorInvalidValue;
+    if (a.nchunks > kSmallConvMaxChunks || lds > kSmallMaxLds || a.wd > S) return hipErrorInvalidValue;
     if (hipError_t e = ensure_dynamic_lds<&conv_small_kernel<KT, NI, HALO, EPI>>(kSmallMaxLds); e != hipSuccess) return e;
     dim3 grid((unsigned)(a.B * a.tiles_per_item), (unsigned)((a.M + 127) / 128));
     note_kernel("conv_small_kernel", KT, NI, HALO, EPI);

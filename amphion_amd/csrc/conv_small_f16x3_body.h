@@ -2,25 +2,10 @@
 // column-tile index, row-group index): conv_small_kernel runs it over a 2-D grid of its own; conv_small3_kernel (conv_small3_f16x3.hip)
 // runs the same conv of a generator stage's three resblocks side by side in ONE grid.
 #pragma once
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 namespace amp {
 
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union FragS {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM_S() __builtin_amdgcn_sched_barrier(0x386)
-// hides a loaded value behind an empty asm: hipcc otherwise turns `cond ? loaded : 0` into a branch around the load
-// (load sunk into the taken side) and, loads returning in order, waits with vmcnt(0) for the whole tile at every one
-#define AMP_OPAQUE(v) asm("" : "+v"(v))
-
-constexpr int kSmallMaxChunks = kSmallConvMaxChunks;   // Cin <= 256
 constexpr size_t kSmallMaxLds = 128 * 1024;
 
 // A-fragment prefetch distance in chunk-sets (8 * KT VGPRs each)
@@ -39,7 +24,7 @@ __device__ __forceinline__ void conv_small_body(const ConvArgs a, const int bx, 
     constexpr int NST = (4 * S) / 256;         // staging items per thread and chunk
     constexpr int BUF = 4 * S;                 // uint4 per chunk buffer: [plane hi|lo][octet h][S]
     constexpr int AR = ARing<KT>::n;
-    constexpr int MAXC = kSmallMaxChunks;
+    constexpr int MAXC = kSmallConvMaxChunks;
     static_assert(S % 64 == 0, "the channel quad of a staging item must be wave-uniform");
     static_assert(AR % 2 == 0, "the B double buffer alternates with (chunk * KT + tap)");
     extern __shared__ __attribute__((aligned(16))) uint4 smem4[];  // [nch_pad][BUF]
@@ -105,7 +90,7 @@ __device__ __forceinline__ void conv_small_body(const ConvArgs a, const int bx, 
     }
 
     const uint4* wa0 = static_cast<const uint4*>(a.wp) + (size_t)(mb_ok ? mb : 0) * nchunks * (KT * 128) + lane;
-    FragS a_h[AR][KT], a_l[AR][KT];
+    Frag a_h[AR][KT], a_l[AR][KT];
 #pragma unroll
     for (int j = 0; j < AR; ++j) {
         const int cj = j < nchunks ? j : nchunks;               // chunk `nchunks` = next block / allocation pad
@@ -278,7 +263,7 @@ __device__ __forceinline__ void conv_small_body(const ConvArgs a, const int bx, 
     const uint4* lbase = smem4 + (hi * S + l31 + a.halo_left + a.off0);
     const int dstep = a.dstep;
     if (mb_ok) {
-        FragS bh[2][NI], bl[2][NI];
+        Frag bh[2][NI], bl[2][NI];
 #pragma unroll
         for (int t = 0; t < NI; ++t) {
             bh[0][t].u = lbase[32 * t];
@@ -303,18 +288,10 @@ __device__ __forceinline__ void conv_small_body(const ConvArgs a, const int bx, 
                         bl[nxt][t].u = bn[2 * S + 32 * t];
                     }
                     __builtin_amdgcn_sched_barrier(0);   // the reads above are issued BEFORE this tap's MFMAs (hipcc sinks them to their use)
-#pragma unroll
-                    for (int t = 0; t < NI; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[j][g].h, bh[cur][t].h, acc[t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < NI; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[j][g].h, bl[cur][t].h, acc[t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < NI; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[j][g].h, bh[cur][t].h, acc[t], 0, 0, 0);
+                    mfma3<NI>(acc, a_h[j][g], a_l[j][g], bh[cur], bl[cur]);
                     a_h[j][g].u = wn_[g * 128];
                     a_l[j][g].u = wn_[g * 128 + 64];
-                    AMP_PIN_VMEM_S();
+                    AMP_PIN_VMEM();
                 }
             }
         }
@@ -383,6 +360,5 @@ __device__ __forceinline__ void conv_small_body(const ConvArgs a, const int bx, 
         }
     }
 }
-
 
 }  // namespace amp

@@ -563,7 +563,7 @@ static int conv_run(const amp_conv* c, const float* x, int B, int T, float slope
     }
     if (c->gated_H) { set_error("amp_conv_forward: a gated conv (amp_conv_create_gated) only runs inside amp_wn_forward"); return AMP_ERR_STATE; }
     if (c->precision == PREC_F16X3 && slope_in > 1.f) {
-        // the f16x3 kernels form leaky_relu-on-load as max(16 x, 16 slope x) (amp_internal.h: stage4_f16)
+        // the f16x3 kernels form leaky_relu-on-load as max(16 x, 16 slope x) (f16x3_device.h: stage4_f16)
         set_error("amp_conv_forward: leaky_relu slope %g > 1 on the input is outside the f16x3 kernels (use AMP_PRECISION_F32)", (double)slope_in);
         return AMP_ERR_UNSUPPORTED;
     }

@@ -2,20 +2,9 @@
 // this workgroup, number of workgroups): pair_f16x3_kernel runs it over a grid of its own; pair3_kernel (pair3_f16x3.hip) runs the bodies
 // of the three resblocks of a generator stage side by side in ONE grid.
 #pragma once
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 namespace amp {
-
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union Frag {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 template <int KT, int WM, int WN, int NI, int SX>
 __device__ __forceinline__ void pair_f16x3_body(const PairArgs& a, const int bid, const int nbx) {
@@ -284,6 +273,5 @@ __device__ __forceinline__ void pair_f16x3_body(const PairArgs& a, const int bid
     }
     if (a.range_flag && __any(range_max > 65504.f) && lane == 0) atomicOr(a.range_flag, 1u);
 }
-
 
 }  // namespace amp

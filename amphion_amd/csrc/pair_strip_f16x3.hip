@@ -30,7 +30,7 @@
 //
 // WM x WN waves x MI row blocks per wave: C = 32 * WM * MI channels (C = 256 runs 8 waves, one workgroup per CU: the xt tile
 // of all 256 channels is 108 KB); compiled once per tap count:  -DAMP_KT=<3|5|7|11>.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -41,18 +41,8 @@
 
 namespace amp {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union FragS {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 // LDS reads stay above, MFMAs below (VALU / SALU / VMEM / LDS writes may cross)
 #define AMP_PIN_DSREAD() __builtin_amdgcn_sched_barrier(0x276)
-
 
 // RING = D > 0 (round 2, third session; `wide` = 3): the A fragments as a ring of D taps per row block instead of a whole chunk's set
 // (conv_blk_f16x3.hip: tap g in slot g % D, re-loaded right after its use with tap g + D of this chunk or tap g % D of the next
@@ -91,11 +81,8 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int hi = lane >> 5, l31 = lane & 31;
-    const int nbx = gridDim.x;  // XCD-contiguous runs of strips, see conv_f16x3.hip
-    // (ragged batches keep the dispatch order: with utterances of different lengths a contiguous run per XCD would hand
-    // one XCD the long utterances and another only tiles that exit at once -- measured 43.8 vs 48.7 ms padded, visit AD)
-    int bx = ((nbx & 7) == 0 && !a.lens) ? (int)(blockIdx.x & 7) * (nbx >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (a.rev) bx = nbx - 1 - bx;   // descending tile order: start where the previous launch stopped writing (PairArgs::rev)
+    const int nbx = gridDim.x;  // XCD-contiguous runs of strips, descending when a.rev: tile_order() in f16x3_device.h
+    int bx = tile_order(blockIdx.x, nbx, a.lens != nullptr, a.rev);
     const int item = bx / a.strips_per_item;
     const int strip = bx - item * a.strips_per_item;
     constexpr int C = 32 * WM * MI;
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     const uint4* wa1 = static_cast<const uint4*>(a.wp1) + (size_t)(MI * wm) * MBS + wlane;
     const uint4* wa2 = static_cast<const uint4*>(a.wp2) + (size_t)(MI * wm) * MBS + wlane;
     constexpr int NA = RING > 0 ? RING : KT;          // A-fragment register sets per row block
-    FragS a_h[MI][NA], a_l[MI][NA];
+    Frag a_h[MI][NA], a_l[MI][NA];
     // after tap g of the chunk at `wcur`: the register set of tap g is re-loaded with the tap it serves next -- the same tap of the
     // next chunk (`wnext`) without a ring; with a ring tap g + RING of this chunk, or tap g % RING of the next chunk
     auto reload = [&](int mi, int g, const uint4* wcur, const uint4* wnext) __attribute__((always_inline)) {
@@ -259,7 +246,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
                 // the B fragments of half-tap h + 1 are read while the MFMAs of half-tap h run (two register sets); the staging loads of the
                 // next chunk are issued behind the first half-tap's MFMAs instead of in front of them (round 5: clock stamps showed the
                 // matrix pipe waiting ~100 cycles for LDS at every half-tap and ~700 for the address arithmetic at every chunk)
-                FragS bh[2][NB], bl[2][NB];
+                Frag bh[2][NB], bl[2][NB];
 #pragma unroll
                 for (int t = 0; t < NB; ++t) {
                     bh[0][t].u = base[32 * t];
@@ -281,15 +268,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
                     AMP_PIN_DSREAD();
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bh[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bl[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[mi][v].h, bh[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
+                        mfma3<NB>(acc[mi] + th * NB, a_h[mi][v], a_l[mi][v], bh[cur], bl[cur]);
                         if (th == BH - 1) reload(mi, g, wcur, wan);
                     }
                     if (h == 0) {
@@ -358,7 +337,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
         // ---------------- conv2 over the xt tile ----------------
         {
             // as in conv1; there is no barrier between the chunks, so the last half-tap of a chunk reads the first of the next one
-            FragS bh[2][NB], bl[2][NB];
+            Frag bh[2][NB], bl[2][NB];
             {
                 const uint4* b0 = xt4 + rd2;
 #pragma unroll
@@ -390,15 +369,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
                     AMP_PIN_DSREAD();
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bh[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[mi][v].h, bl[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
-#pragma unroll
-                        for (int t = 0; t < NB; ++t)
-                            acc[mi][th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[mi][v].h, bh[cur][t].h, acc[mi][th * NB + t], 0, 0, 0);
+                        mfma3<NB>(acc[mi] + th * NB, a_h[mi][v], a_l[mi][v], bh[cur], bl[cur]);
                         if (th == BH - 1) reload(mi, g, wcur, wan);
                     }
                     if (th == BH - 1) AMP_PIN_VMEM();
@@ -449,7 +420,6 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     }
     if (a.range_flag && __any(range_max > 65504.f) && lane == 0) atomicOr(a.range_flag, 1u);
 }
-
 
 template <int KT, int WM, int WN, int NI, int SX, int MI = 1, int RING = 0, int SBUF = 2>
 static hipError_t launch_strip_one(const PairArgs& a, hipStream_t stream) {

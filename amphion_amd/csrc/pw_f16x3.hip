@@ -23,18 +23,10 @@
 #include <algorithm>
 #include <memory>
 
-#include "amp_internal.h"
+#include "f16x3_device.h"
 #include "gelu_erf.h"
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union PwFrag {
-    uint4 u;
-    f16x8 h;
-};
 
 constexpr int PW_KS = 4;            // MFMA k-extents (16 channels each) per K step
 constexpr int PW_KC = 16 * PW_KS;   // channels per K step
@@ -55,8 +47,6 @@ struct PwArgs {
     float inv_scale;      // 1 / (16 * 2^s)
     unsigned* range_flag;
 };
-
-#define AMP_PW_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 template <int EPI, int MI, int NI>
 __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
     // A fragments of one K step: [k-extent][row block][plane]; entry (mb, c16, plane) of the pack at ((mb * nc16 + c16) * 2 + plane) * 64
     const uint4* wa = a.wp + (size_t)mb0 * a.nc16 * 128 + lane;
     const size_t mbs = (size_t)a.nc16 * 128;           // uint4 per row block
-    PwFrag ah[PW_KS][MI], al[PW_KS][MI];
+    Frag ah[PW_KS][MI], al[PW_KS][MI];
 #pragma unroll
     for (int h = 0; h < PW_KS; ++h)
 #pragma unroll
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
             al[h][i].u = wa[i * mbs + h * 128 + 64];
         }
     stage_load(0);
-    AMP_PW_PIN_VMEM();
+    AMP_PIN_VMEM();
     stage_store(0, 0);
     __syncthreads();
 
@@ -144,14 +134,14 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
     auto step = [&](const int s, const bool more) __attribute__((always_inline)) {
         if (more) {
             stage_load(s + 1);
-            AMP_PW_PIN_VMEM();
+            AMP_PIN_VMEM();
         }
         wa += PW_KS * 128;
         const uint4* base = pw_smem + (s & 1) * BUF + rd0;
 #pragma unroll
         for (int h = 0; h < PW_KS; ++h) {
             const uint4* bg = base + (2 * h) * TN;
-            PwFrag bh[NI], bl[NI];
+            Frag bh[NI], bl[NI];
 #pragma unroll
             for (int t = 0; t < NI; ++t) {
                 bh[t].u = bg[32 * t];
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
                     ah[h][i].u = wa[i * mbs + h * 128];
                     al[h][i].u = wa[i * mbs + h * 128 + 64];
                 }
-                AMP_PW_PIN_VMEM();
+                AMP_PIN_VMEM();
             }
         }
         if (more) stage_store(s + 1, (s + 1) & 1);

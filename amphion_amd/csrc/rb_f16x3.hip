@@ -35,23 +35,13 @@
 // the same dot product, computed in another row of the tile: same bits).
 //
 // Compiled once per tap count:  -DAMP_KT=<3|5|7|11>.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 
 #ifndef AMP_KT
 #error "compile with -DAMP_KT=<taps>"
 #endif
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union FragR {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 // RB_G guard columns either side of the LDS tile (>= (k-1)/2 * max dilation): 32, or 16 where the tile of all channels would not
 // fit otherwise (C = 128: 8 chunks x 64 B x (256 + 2 x 16) columns = 147 KB)
@@ -77,9 +67,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int hi = lane >> 5, l31 = lane & 31;
-    const int nbx = gridDim.x;  // XCD-contiguous tile runs, see conv_f16x3.hip (ragged batches keep the dispatch order)
-    int bx = ((nbx & 7) == 0 && !a.lens) ? (int)(blockIdx.x & 7) * (nbx >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (a.rev) bx = nbx - 1 - bx;   // descending tile order, PairArgs::rev
+    const int nbx = gridDim.x;  // XCD-contiguous tile runs, tile_order() in f16x3_device.h
+    int bx = tile_order(blockIdx.x, nbx, a.lens != nullptr, a.rev);
     const int item = bx / a.tiles_per_item;
     const int tile = bx - item * a.tiles_per_item;
     const int T = a.T;
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
     // during a conv's last chunk fetches the next conv's first chunk
     constexpr size_t MBS = (size_t)NCH * (KT * 128);
     constexpr int NA = RING > 0 ? RING : KT;  // A-fragment register sets
-    FragR a_h[NA], a_l[NA];
+    Frag a_h[NA], a_l[NA];
     // the packed fragment this lane fetches: A row (lane & 31) = 8 a + 4 b + j holds weight row 16 b + 4 a + j
     const int wlane = (lane & 32) | (16 * ((lane >> 2) & 1) + 4 * ((lane >> 3) & 3) + (lane & 3));
     {
@@ -180,21 +169,13 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
                 constexpr int NB = NI / 2;      // the tap's B fragments in two halves (16 registers instead of 32)
 #pragma unroll
                 for (int th = 0; th < 2; ++th) {
-                    FragR bh[NB], bl[NB];
+                    Frag bh[NB], bl[NB];
 #pragma unroll
                     for (int t = 0; t < NB; ++t) {
                         bh[t].u = bg[32 * (th * NB + t)];
                         bl[t].u = bg[2 * WL + 32 * (th * NB + t)];
                     }
-#pragma unroll
-                    for (int t = 0; t < NB; ++t)
-                        acc[th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[v].h, bh[t].h, acc[th * NB + t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < NB; ++t)
-                        acc[th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[v].h, bl[t].h, acc[th * NB + t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < NB; ++t)
-                        acc[th * NB + t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[v].h, bh[t].h, acc[th * NB + t], 0, 0, 0);
+                    mfma3<NB>(acc + th * NB, a_h[v], a_l[v], bh, bl);
                 }
                 {   // this tap's register set is free: fetch the tap it serves next
                     const bool same = RING > 0 && g + RING < KT;

@@ -4,7 +4,7 @@
 //   bits: 2 no chunk barriers | 4 no A-fragment reloads | 8 no staging loads | 16 no residual loads | 32 no conv1 MFMAs
 //         64 no conv2 MFMAs | 128 B fragments always tap 0 (LDS broadcast-free same address) | 256 seam without split
 // Regenerate with tests/experiments/make_pair_ablate.py after editing the product kernel.
-#include "amp_internal.h"
+#include "f16x3_device.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -34,16 +34,6 @@ __device__ __forceinline__ f32x16_ mf_keep(f16x8_ a, f16x8_ b, f32x16_ c) { asm 
 #endif
 
 namespace amp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-union Frag {
-    uint4 u;
-    f16x8 h;
-};
-
-#define AMP_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x386)
 
 template <int KT, int WM, int WN, int NI, int SX>
 __global__ __launch_bounds__(256, 2) void pair_f16x3_kernel(const PairArgs a) {

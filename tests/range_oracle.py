@@ -1,6 +1,6 @@
 """fp64 predictor of the f16x3 range guard: the largest |operand| each conv of an op stages.
 
-The f16x3 kernels stage every conv operand as hi + lo f16 after an exact x16 (amp_internal.h: stage4_f16, seam4_f16; the
+The f16x3 kernels stage every conv operand as hi + lo f16 after an exact x16 (f16x3_device.h: stage4_f16, seam4_f16; the
 Activation1d outputs of ampb_f16x3.hip): |x| <= 4094 fits (x16 = 65504, the largest finite f16), anything beyond, and any
 infinity, raises the range flag.  A NaN operand is not flagged (it reaches the output as it does through the reference).
 The operand of a conv is what the kernel stages, not what the layer receives: the value AFTER the on-load leaky ReLU, the
