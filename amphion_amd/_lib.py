@@ -76,6 +76,18 @@ class amp_mel_desc(ctypes.Structure):
         super().__init__(ctypes.sizeof(type(self)), *args, **kw)
 
 
+class amp_dw_desc(ctypes.Structure):
+    _fields_ = [
+        ("residual_channels", c_int32),
+        ("residual_layers", c_int32),
+        ("dilation_cycle_length", c_int32),
+        ("n_mel", c_int32),
+        ("upsample0", c_int32),
+        ("upsample1", c_int32),
+        ("max_steps", c_int32),
+    ]
+
+
 _SIGNATURES = {
     "amp_version": (c_int, []),
     "amp_last_error": (c_char_p, []),
@@ -112,6 +124,21 @@ _SIGNATURES = {
     "amp_pw_forward": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "amp_pw_precision": (c_int, [c_void_p]),
     "amp_pw_destroy": (None, [c_void_p]),
+    "amp_dw_create": (c_int, [POINTER(amp_dw_desc), POINTER(c_void_p)]),
+    "amp_dw_set_weight": (c_int, [c_void_p, c_char_p, c_void_p, ctypes.c_longlong]),
+    "amp_dw_finalize": (c_int, [c_void_p]),
+    "amp_dw_precision": (c_int, [c_void_p]),
+    "amp_dw_set_precision": (c_int, [c_void_p, c_int]),
+    "amp_dw_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_dw_condition": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_dw_embed": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "amp_dw_input": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "amp_dw_layer": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "amp_dw_tail": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "amp_dw_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_dw_sample_step": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                   c_size_t, c_void_p]),
+    "amp_dw_destroy": (None, [c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),

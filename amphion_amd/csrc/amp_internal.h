@@ -161,6 +161,31 @@ struct AmpbArgs {
     unsigned* range_flag;      // see ConvArgs
 };
 
+// Arguments of the DiffWave residual-layer kernels (dw_layer_f16x3.hip), diffwave.py:112-124 in one launch
+constexpr int DW_TN = 64;   // output columns per workgroup
+struct DwLayerArgs {
+    const float* x;            // [B, C, L] input and residual
+    const float* cond;         // [B, n_mel, L] up-sampled spectrogram (fp32, as the up-sampler writes it)
+    const float* dconst;       // [C] diffusion_projection(e) per item (batch stride dconst_bs; 0 = one row for the whole batch)
+    long long dconst_bs;
+    const float* skip_in;      // [B, C, L] running skip sum or nullptr (first layer); may alias skip_out
+    float* x_out;              // [B, C, L]; must NOT alias x (other tiles read x at +- d)
+    float* skip_out;           // [B, C, L]
+    const uint4* wp1;          // f16x3: [2C, 3C + n_mel] (taps, then conditioner) as packed A fragments
+    const uint4* wp2;          //        [2C, C]
+    const float* w1f;          // f32: the same two matrices, row-major, K unpadded
+    const float* w2f;
+    const float* bias1;        // [2C] dilated_conv.bias + conditioner_projection.bias
+    const float* bias2;        // [2C]
+    int C, n_mel, L, d;
+    int K16;                   // f16x3: ceil((3C + n_mel) / 16), set by the launcher
+    int tiles_per_item;        // set by the launcher
+    float inv1, inv2;          // 1 / (16 * 2^s) of each matrix
+    unsigned* range_flag;      // see ConvArgs
+};
+size_t dw_layer_lds_bytes(int C, int n_mel, bool f32);
+hipError_t launch_dw_layer(DwLayerArgs a, int B, bool f32, hipStream_t stream);
+
 struct ConvPlan {
     int KT;      // taps compiled into the kernel (1,2,3,5,7,11)
     int WM, WN;  // waves along M / N (WM*WN == 4)

@@ -12,6 +12,7 @@ it cannot be shadowed -- it is patched.
 """
 import importlib.abc
 import importlib.util
+import os
 import sys
 
 TARGETS = ("models.vocoders.vocoder_inference", "models.codec.codec_inference")
@@ -39,6 +40,11 @@ CODEC_CLASS_TARGETS = {
 }
 
 
+# DiffWave is opt-in: AMP_HOOK_DIFFWAVE=1 in the environment (read once, by the first install()) or install(diffwave=True) make
+# install_into_reference overwrite the three `diffwave` registry entries too; without it they stay the reference's.
+_DIFFWAVE = None
+
+
 def _patch_classes(module, fullname, targets=CLASS_TARGETS):
     import importlib
 
@@ -64,12 +70,12 @@ class _PatchLoader(importlib.abc.Loader):
             return
         from amphion_amd.models.vocoders.vocoder_inference import install_into_reference
 
-        install_into_reference(module)
+        install_into_reference(module, diffwave=bool(_DIFFWAVE))
         module.__amphion_amd_patched__ = True
         for other in TARGETS:       # a target imported while this finder was busy resolving another one
             m = sys.modules.get(other)
             if m is not None and hasattr(m, "_vocoders") and not getattr(m, "__amphion_amd_patched__", False):
-                install_into_reference(m)
+                install_into_reference(m, diffwave=bool(_DIFFWAVE))
                 m.__amphion_amd_patched__ = True
 
 
@@ -143,14 +149,19 @@ def _install_codec():
         sys.meta_path.insert(0, _CodecFinder(pending))
 
 
-def install():
+def install(diffwave=None):
+    global _DIFFWAVE
+    if diffwave is not None:
+        _DIFFWAVE = bool(diffwave)
+    elif _DIFFWAVE is None:
+        _DIFFWAVE = os.environ.get("AMP_HOOK_DIFFWAVE", "") == "1"
     _install_codec()
     from_loaded = [t for t in TARGETS if t in sys.modules]
     if from_loaded:
         from amphion_amd.models.vocoders.vocoder_inference import install_into_reference
 
         for t in from_loaded:
-            install_into_reference(sys.modules[t])
+            install_into_reference(sys.modules[t], diffwave=_DIFFWAVE)
             sys.modules[t].__amphion_amd_patched__ = True
     cls_loaded = [t for t in CLASS_TARGETS if t in sys.modules]
     for t in cls_loaded:

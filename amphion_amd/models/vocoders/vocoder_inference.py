@@ -44,12 +44,27 @@ _vocoder_infer_funcs = {
 }
 
 
-def install_into_reference(ref_module):
-    """Point the reference module's registries at the MI355X implementations."""
+def diffwave_entries():
+    """the three registry entries of DiffWave (vocoder_inference.py:41,55,68).  They are opt-in (``install_into_reference(...,
+    diffwave=True)``): the GAN registries above are what the hook installs by default."""
+    from amphion_amd.models.vocoders.diffusion import diffusion_vocoder_inference
+    from amphion_amd.models.vocoders.diffusion.diffwave import diffwave
+
+    return diffwave.DiffWave, diffusion_vocoder_inference.vocoder_inference, diffusion_vocoder_inference.synthesis_audios
+
+
+def install_into_reference(ref_module, diffwave=False):
+    """Point the reference module's registries at the MI355X implementations; ``diffwave=True`` also overwrites the three
+    ``diffwave`` entries."""
     for name in _vocoders:
         ref_module._vocoders[name] = _vocoders[name]
         ref_module._vocoder_forward_funcs[name] = _vocoder_forward_funcs[name]
         ref_module._vocoder_infer_funcs[name] = _vocoder_infer_funcs[name]
+    if diffwave:
+        cls, fwd, infer = diffwave_entries()
+        ref_module._vocoders["diffwave"] = cls
+        ref_module._vocoder_forward_funcs["diffwave"] = fwd
+        ref_module._vocoder_infer_funcs["diffwave"] = infer
     return ref_module
 
 

@@ -93,7 +93,8 @@ typedef struct amp_gen amp_gen;
  * policy never chose), refuses amp_set_pair_strips(1), and lets amp_mel_forward / amp_mel_backward / amp_istft_forward / amp_istft_same take
  * any n_fft in [64, 4096] (mixed-radix kernels: compile-time butterflies for the primes 2 .. 13, a run-time radix pass for larger prime factors;
  * powers of two keep their kernels); 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision /
- * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024). */
+ * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024); 144 (additive): the DiffWave entry
+ * points amp_dw_*. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -577,6 +578,49 @@ int amp_pw_forward(const amp_pw* p, const float* x_dev, long long x_batch_stride
 /* the precision the handle was created with (AMP_PRECISION_*), -1 for NULL */
 int amp_pw_precision(const amp_pw* p);
 void amp_pw_destroy(amp_pw* p);
+
+/* ---- DiffWave (csrc/diffwave.hip, csrc/dw_layer_f16x3.hip): models/vocoders/diffusion/diffwave/diffwave.py:127-179 and one step of the
+ * sampler of models/vocoders/diffusion/diffusion_vocoder_inference.py:55-71.  L = F * upsample0 * upsample1 samples per item.
+ *   amp_dw_create / amp_dw_set_weight / amp_dw_finalize: weights under the reference's state_dict keys (flattened fp32, `count`
+ *     elements), plus the non-persistent buffer "diffusion_embedding.embedding" [max_steps, 128].  Refused: residual_channels not a
+ *     multiple of 32 or above 128, odd upsample factors.  The arithmetic is taken from amp_set_precision at creation;
+ *     amp_dw_set_precision switches a handle later (both weight forms are kept: the sampler repeats an out-of-range call in fp32).
+ *   amp_dw_condition: SpectrogramUpsampler, mel [B, n_mel, F] -> cond [B, n_mel, L]; once per utterance.
+ *   amp_dw_forward: eps [B, L] = DiffWave.forward(audio [B, L], steps, mel) from cond; steps_dev holds n_steps = 1 or B FLOAT step
+ *     values on the device (an integer step is its float value; fractional steps interpolate the embedding table).
+ *   amp_dw_sample_step: audio = clamp(c1 * (audio - c2 * eps(audio, step)) + sigma * noise, -1, 1) in place; noise_dev NULL = none.
+ *   op level (what forward chains, bit for bit): amp_dw_embed -> dconst [n_steps, N, C] (diffusion_projection of every layer),
+ *     amp_dw_input -> relu(input_projection(audio)) [B, C, L], amp_dw_layer (one ResidualBlock, diffwave.py:112-124: dconst_dev points
+ *     at the layer's [C] row, dconst_batch_stride elements between items, 0 = shared; skip_in_dev NULL for the first layer, may equal
+ *     skip_out_dev; x_out_dev must not overlap x_dev), amp_dw_tail -> eps [B, L] from the skip sum.
+ * Every launch goes to `stream`; no allocation, no synchronisation.  ws_dev: amp_dw_workspace_bytes(B, F) bytes.  Under f16x3 the layer
+ * kernel feeds the op-level range flag (amp_range_check).  Deterministic; a batch row does not depend on the rest of the batch. ---- */
+typedef struct amp_dw amp_dw;
+typedef struct amp_dw_desc {
+    int32_t residual_channels;      /* cfg.model.diffwave.residual_channels */
+    int32_t residual_layers;
+    int32_t dilation_cycle_length;
+    int32_t n_mel;                  /* cfg.preprocess.n_mel */
+    int32_t upsample0, upsample1;   /* cfg.model.diffwave.upsample_factors */
+    int32_t max_steps;              /* len(noise_schedule) */
+} amp_dw_desc;
+int amp_dw_create(const amp_dw_desc* desc, amp_dw** out);
+int amp_dw_set_weight(amp_dw* h, const char* key, const float* data_host, long long count);
+int amp_dw_finalize(amp_dw* h);
+int amp_dw_precision(const amp_dw* h);
+int amp_dw_set_precision(amp_dw* h, int precision);
+size_t amp_dw_workspace_bytes(const amp_dw* h, int B, int F);
+int amp_dw_condition(const amp_dw* h, const float* mel_dev, int B, int F, float* cond_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int amp_dw_embed(const amp_dw* h, const float* steps_dev, int n_steps, float* dconst_dev, void* stream);
+int amp_dw_input(const amp_dw* h, const float* audio_dev, int B, int L, float* x_dev, void* stream);
+int amp_dw_layer(const amp_dw* h, int layer, const float* x_dev, const float* cond_dev, const float* dconst_dev, long long dconst_batch_stride,
+                 const float* skip_in_dev, float* x_out_dev, float* skip_out_dev, int B, int L, void* stream);
+int amp_dw_tail(const amp_dw* h, const float* skip_dev, int B, int L, float* eps_dev, void* stream);
+int amp_dw_forward(const amp_dw* h, const float* audio_dev, int L, const float* steps_dev, int n_steps, const float* cond_dev, int B, int F,
+                   float* eps_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int amp_dw_sample_step(const amp_dw* h, float* audio_dev, int L, float step, float c1, float c2, float sigma, const float* noise_dev,
+                       const float* cond_dev, int B, int F, void* ws_dev, size_t ws_bytes, void* stream);
+void amp_dw_destroy(amp_dw* h);
 
 #ifdef __cplusplus
 }
