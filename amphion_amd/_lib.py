@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -238,6 +239,24 @@ def check(status):
     if status < 0:
         raise AmpError(status, lib().amp_last_error().decode("utf-8", "replace"))
     return status
+
+
+def ptr(t):
+    """``t.data_ptr()`` as a ``c_void_p`` argument; None (an absent optional tensor) stays None"""
+    return c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _destroy(name, address):
+    try:
+        getattr(lib(), name)(c_void_p(address))
+    except Exception:  # interpreter shutdown
+        pass
+
+
+def finalizer(owner, destroy, handle):
+    """A ``weakref.finalize`` that releases ``handle`` (a ``c_void_p``) through the entry point named ``destroy`` ("amp_*_destroy")
+    when ``owner`` is collected, or when called -- once either way."""
+    return weakref.finalize(owner, _destroy, destroy, handle.value)
 
 
 AMP_ERR_UNSUPPORTED = -4

@@ -37,7 +37,8 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE,
 
 
 def _units():
-    units = [("generator.hip", "generator.o", []), ("small_kernels.hip", "small_kernels.o", []),
+    units = [("runtime.hip", "runtime.o", []), ("conv_host.hip", "conv_host.o", []), ("generator.hip", "generator.o", []),
+             ("ops_abi.hip", "ops_abi.o", []), ("small_kernels.hip", "small_kernels.o", []),
              ("mel.hip", "mel.o", []), ("vits_text.hip", "vits_text.o", []), ("pair3_f16x3.hip", "pair3_f16x3.o", []),
              ("conv_small3_f16x3.hip", "conv_small3_f16x3.o", []),
              ("pw_f16x3.hip", "pw_f16x3.o", []), ("dw_layer_f16x3.hip", "dw_layer_f16x3.o", []), ("diffwave.hip", "diffwave.o", [])]
@@ -85,7 +86,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     units = _units()
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         objs = list(ex.map(_compile, units))
-    # --no-undefined: a tap count generator.hip dispatches to but the lists above do not build fails here, not at dlopen
+    # --no-undefined: a tap count conv_host.hip dispatches to but the lists above do not build fails here, not at dlopen
     cmd = [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-Wl,--no-undefined", "-o", LIB] + [os.path.join(OBJ, o) for o in objs]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

@@ -27,7 +27,7 @@ enum { PREC_F32 = 0, PREC_F16X3 = 1 };
 //                        the result is scattered to n = q*up + r - up_pad.
 struct ConvArgs {
     const float* x;      // [B, Cin, Tin]
-    const void* wp;      // packed A fragments (f32, or f16 hi/lo planes for f16x3), see conv_build()
+    const void* wp;      // packed A fragments (f32, or f16 hi/lo planes for f16x3), see conv_build() in conv_host.hip
     const float* bias;   // [Cout] or nullptr
     const float* res;    // [B, Cout, Tout] or nullptr (may alias y)
     float* y;            // [B, Cout, Tout]
@@ -200,7 +200,7 @@ struct ConvPlan {
 bool choose_plan(int ntaps, int M, int halo_total, int Tq, ConvPlan* plan);
 
 // ---- per-tap-count kernels: each TU below is compiled once per tap count (-DAMP_KT=k, the lists in build.py) and instantiates these
-// templates for KT = AMP_KT only; generator.hip maps a runtime tap count onto them
+// templates for KT = AMP_KT only; conv_host.hip maps a runtime tap count onto them
 template <int KT> hipError_t launch_conv(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);        // exact f32 MFMA (conv_mfma.hip)
 template <int KT> hipError_t launch_conv_f16x3(const ConvPlan& plan, const ConvArgs& a, hipStream_t stream);  // split-f16 MFMA (conv_f16x3.hip)
 // row-blocked conv (conv_blk_f16x3.hip): tile width for cm chunks per staging round and a halo, 0 = not covered; launch
@@ -343,7 +343,7 @@ inline void note_conv_work(const ConvArgs& a, int KT, dim3 grid) {
 }
 
 // The f16x3 kernels stage fp32 activations as hi + lo f16 pairs after an exact x16: anything beyond |x| = 4094 (or
-// non-finite) cannot be represented.  They OR 1 into this per-device word when that happens (range_guard.hip).
+// non-finite) cannot be represented.  They OR 1 into this per-device word when that happens (runtime.hip; amp_host.h: RangeGuard).
 unsigned* range_flag_for_current_device();
 // (the kernels keep the running maximum of |staged value|: one v_max_f32 per element; a NaN operand is not flagged --
 // it propagates to the output exactly as it does through the fp32 reference)

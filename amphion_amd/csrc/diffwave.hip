@@ -8,7 +8,7 @@
 #include <memory>
 #include <string>
 
-#include "amp_internal.h"
+#include "amp_host.h"
 
 namespace amp {
 
@@ -144,15 +144,6 @@ __global__ __launch_bounds__(256) void dw_tail_kernel(const DwTailArgs a) {
 
 using namespace amp;
 
-#define DW_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);     \
-            return AMP_ERR_HIP;                                                                        \
-        }                                                                                              \
-    } while (0)
-
 struct DwLayer {
     uint4 *wp1 = nullptr, *wp2 = nullptr;
     float *w1f = nullptr, *w2f = nullptr, *b1 = nullptr, *b2 = nullptr;
@@ -177,37 +168,18 @@ struct amp_dw {
 };
 
 static int dw_upload(amp_dw* h, const void* host, size_t bytes, void** out) {
-    void* p = nullptr;
-    DW_HIP(hipMalloc(&p, bytes));
-    h->owned.push_back(p);
-    DW_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-    *out = p;
+    AMP_RC(device_upload(host, bytes, out));
+    h->owned.push_back(*out);
     return AMP_OK;
 }
 
-// [rows, cols] fp32 -> f16x3 A fragments [row block][k16][plane hi | lo][lane][8 x f16] after a per-matrix 2^s (max |w| in (2^12, 2^13]),
-// the pack of amp_pw_create
+// [rows, cols] fp32 (rows a multiple of 32) -> f16x3 A fragments after a per-matrix 2^s (amp_host.h: pack_a_f16x3)
 static std::vector<_Float16> dw_pack(const std::vector<float>& W, int rows, int cols, float* inv_scale) {
     float wmax = 0.f;
     for (float v : W) wmax = fmaxf(wmax, fabsf(v));
-    int e2 = 0;
-    if (wmax > 0.f) { (void)frexpf(wmax, &e2); if (ldexpf(1.f, e2 - 1) == wmax) e2 -= 1; }
-    const float wscale = wmax > 0.f ? ldexpf(1.f, 13 - e2) : 1.f;
+    const float wscale = pow2_weight_scale(wmax);
     *inv_scale = 1.f / (16.f * wscale);
-    const int nk = (cols + 15) / 16, nmb = rows / 32;
-    std::vector<_Float16> wp((size_t)nmb * nk * 2 * 64 * 8, (_Float16)0.f);
-    for (int mb = 0; mb < nmb; ++mb)
-        for (int k = 0; k < nk; ++k)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int m = mb * 32 + (lane & 31), i = k * 16 + 8 * (lane >> 5) + e;
-                    const float v = i < cols ? W[(size_t)m * cols + i] * wscale : 0.f;
-                    const _Float16 hi = (_Float16)v;
-                    const size_t ent = ((size_t)mb * nk + k) * 2;
-                    wp[((ent + 0) * 64 + lane) * 8 + e] = hi;
-                    wp[((ent + 1) * 64 + lane) * 8 + e] = (_Float16)(v - (float)hi);
-                }
-    return wp;
+    return pack_a_f16x3(rows / 32, (cols + 15) / 16, 1, 0, wscale, [&](int m, int i, int) { return i < cols ? W[(size_t)m * cols + i] : 0.f; });
 }
 
 static bool dw_overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -238,7 +210,7 @@ static int dw_layer_run(const amp_dw* h, int layer, const float* x, const float*
     a.inv1 = ly.inv1; a.inv2 = ly.inv2;
     const bool f32 = h->precision == PREC_F32;
     a.range_flag = f32 ? nullptr : range_flag_for_current_device();
-    DW_HIP(launch_dw_layer(a, B, f32, stream));
+    AMP_HIP(launch_dw_layer(a, B, f32, stream));
     return AMP_OK;
 }
 
@@ -251,7 +223,7 @@ static int dw_embed_run(const amp_dw* h, const float* steps_dev, int S, float st
     note_work((unsigned)S, 2.0 * S * (128.0 * 512 + 512.0 * 512 + 512.0 * a.NC) / 1e9, 4.0 * (128.0 * 512 + 512.0 * 512 + 512.0 * a.NC) / 1e6,
               "diffwave step embedding S=%d -> [%d, %d]", S, h->d.residual_layers, h->d.residual_channels);
     hipLaunchKernelGGL(dw_embed_kernel, dim3((unsigned)S), dim3(512), 0, stream, a);
-    DW_HIP(hipGetLastError());
+    AMP_HIP(hipGetLastError());
     return AMP_OK;
 }
 
@@ -262,7 +234,7 @@ static int dw_input_run(const amp_dw* h, const float* audio, int B, int L, float
     note_kernel("dw_input_kernel");
     note_work(nb, 2.0 * n / 1e9, 4.0 * ((double)B * L + n) / 1e6, "diffwave input projection 1->%d L=%d B=%d", C, L, B);
     hipLaunchKernelGGL(dw_input_kernel, dim3(nb), dim3(256), 0, stream, audio, h->in_w, h->in_b, x, C, L, n);
-    DW_HIP(hipGetLastError());
+    AMP_HIP(hipGetLastError());
     return AMP_OK;
 }
 
@@ -283,7 +255,7 @@ static int dw_tail_run(const amp_dw* h, const float* skip, int B, int L, float* 
         case 96: hipLaunchKernelGGL(dw_tail_kernel<96>, dim3(nb), dim3(256), 0, stream, a); break;
         default: hipLaunchKernelGGL(dw_tail_kernel<128>, dim3(nb), dim3(256), 0, stream, a); break;
     }
-    DW_HIP(hipGetLastError());
+    AMP_HIP(hipGetLastError());
     return AMP_OK;
 }
 
@@ -480,11 +452,11 @@ int amp_dw_condition(const amp_dw* h, const float* mel_dev, int B, int F, float*
     note_kernel("dw_upsample_kernel");
     note_work((n0 + 255) / 256, 12.0 * n0 / 1e9, 4.0 * ((double)B * M * F + n0) / 1e6, "diffwave upsampler x%d F=%d B=%d", u0, F, B);
     hipLaunchKernelGGL(dw_upsample_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, stream, mel_dev, mid, h->up_w[0], h->up_b[0], M, F, u0, n0);
-    DW_HIP(hipGetLastError());
+    AMP_HIP(hipGetLastError());
     note_kernel("dw_upsample_kernel");
     note_work((n1 + 255) / 256, 12.0 * n1 / 1e9, 4.0 * ((double)n0 + n1) / 1e6, "diffwave upsampler x%d F=%d B=%d", u1, F * u0, B);
     hipLaunchKernelGGL(dw_upsample_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, stream, mid, cond_dev, h->up_w[1], h->up_b[1], M, F * u0, u1, n1);
-    DW_HIP(hipGetLastError());
+    AMP_HIP(hipGetLastError());
     return AMP_OK;
 }
 

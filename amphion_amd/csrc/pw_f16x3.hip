@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "amp_host.h"
 #include "f16x3_device.h"
 #include "gelu_erf.h"
 
@@ -258,18 +259,9 @@ struct amp_pw {
     ~amp_pw() {
         if (wp_dev) (void)hipFree(wp_dev);
         if (bias_dev) (void)hipFree(bias_dev);
-        if (conv) amp_conv_destroy(conv);
+        delete conv;
     }
 };
-
-#define PW_HIP(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);     \
-            return AMP_ERR_HIP;                                                                        \
-        }                                                                                              \
-    } while (0)
 
 extern "C" {
 
@@ -284,41 +276,24 @@ int amp_pw_create(int cin, int cout, const float* weight_host, const float* bias
     if (bias_host) std::copy(bias_host, bias_host + cout, bias.begin());
     if (p->precision == PREC_F32) {
         // [cout, cin] is the Conv1d weight [cout, cin, 1]
-        if (int rc = amp_conv_create(0, cin, cout, 1, 1, 1, 0, weight_host, bias.data(), &p->conv); rc != AMP_OK) return rc;
+        if (amp_device_count() <= 0) { set_error("amp_pw_create: no HIP device visible (the HIP path has no CPU fallback)"); return AMP_ERR_HIP; }
+        p->conv = new amp_conv;
+        p->conv->cin = cin; p->conv->cout = cout; p->conv->k = 1;
+        AMP_RC(conv_build(p->conv, weight_host, bias.data()));
     } else {
-        // per-matrix 2^s: max|w| in (2^12, 2^13], as conv_build does
         float wmax = 0.f;
         const size_t nw = (size_t)cin * cout;
         for (size_t i = 0; i < nw; ++i) wmax = fmaxf(wmax, fabsf(weight_host[i]));
         if (!(wmax < 1e30f)) { set_error("amp_pw_create: non-finite weight"); return AMP_ERR_INVALID; }
-        int e2 = 0;
-        if (wmax > 0.f) { (void)frexpf(wmax, &e2); if (ldexpf(1.f, e2 - 1) == wmax) e2 -= 1; }
-        const float wscale = wmax > 0.f ? ldexpf(1.f, 13 - e2) : 1.f;
+        const float wscale = pow2_weight_scale(wmax);
         p->inv_scale = 1.f / (16.f * wscale);
         p->nsteps = (cin + PW_KC - 1) / PW_KC;
-        const int nc16 = p->nsteps * PW_KS;
         const int nmb = (cout + PW_MROWS - 1) / PW_MROWS * (PW_MROWS / 32);
-        // [row block][k16][plane hi | lo][lane][8 x f16]: lane l holds row 32 mb + (l & 31), channels 16 c16 + 8 (l >> 5) + 0..7
-        const size_t n16 = (size_t)nmb * nc16 * 2 * 64 * 8;
-        std::vector<_Float16> wp(n16, (_Float16)0.f);
-        for (int mb = 0; mb < nmb; ++mb)
-            for (int c16 = 0; c16 < nc16; ++c16)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int m = mb * 32 + (lane & 31);
-                    for (int e = 0; e < 8; ++e) {
-                        const int i = c16 * 16 + 8 * (lane >> 5) + e;
-                        const float v = (m < cout && i < cin) ? weight_host[(size_t)m * cin + i] * wscale : 0.f;
-                        const _Float16 h = (_Float16)v;
-                        const _Float16 l = (_Float16)(v - (float)h);
-                        const size_t ent = ((size_t)mb * nc16 + c16) * 2;
-                        wp[((ent + 0) * 64 + lane) * 8 + e] = h;
-                        wp[((ent + 1) * 64 + lane) * 8 + e] = l;
-                    }
-                }
-        PW_HIP(hipMalloc((void**)&p->wp_dev, n16 * sizeof(_Float16)));
-        PW_HIP(hipMemcpy(p->wp_dev, wp.data(), n16 * sizeof(_Float16), hipMemcpyHostToDevice));
-        PW_HIP(hipMalloc((void**)&p->bias_dev, (size_t)cout * sizeof(float)));
-        PW_HIP(hipMemcpy(p->bias_dev, bias.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
+        const std::vector<_Float16> wp = pack_a_f16x3(nmb, p->nsteps * PW_KS, 1, 0, wscale, [&](int m, int i, int) {
+            return (m < cout && i < cin) ? weight_host[(size_t)m * cin + i] : 0.f;
+        });
+        AMP_RC(device_upload(wp.data(), wp.size() * sizeof(_Float16), (void**)&p->wp_dev));
+        AMP_RC(device_upload(bias.data(), (size_t)cout * sizeof(float), (void**)&p->bias_dev));
     }
     *out = p.release();
     return AMP_OK;
@@ -350,9 +325,9 @@ int amp_pw_forward(const amp_pw* p, const float* x_dev, long long x_batch_stride
         // y aliasing res: Wx + b goes to a stream-ordered temporary of this call (allocated and freed on `stream`, so a handle holds
         // no mutable state and two streams may share it)
         float* tmp = nullptr;
-        if (epilogue == AMP_PW_SCALE_RES && res_dev == y_dev) PW_HIP(hipMallocAsync((void**)&tmp, n * sizeof(float), stream));
+        if (epilogue == AMP_PW_SCALE_RES && res_dev == y_dev) AMP_HIP(hipMallocAsync((void**)&tmp, n * sizeof(float), stream));
         float* dst = tmp ? tmp : y_dev;
-        int rc = amp_conv_forward_strided(p->conv, x_dev, x_batch_stride, B, T, 1.f, nullptr, 1.f, dst, stream_);
+        int rc = conv_run(p->conv, x_dev, B, T, 1.f, nullptr, 1.f, dst, 0, 1.f, stream, x_batch_stride);
         if (rc == AMP_OK && epilogue != AMP_PW_BIAS) {
             note_kernel("pw_epilogue_kernel");
             const unsigned nb = (unsigned)((n + 255) / 256);

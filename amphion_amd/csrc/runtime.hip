@@ -1,0 +1,276 @@
+// Process-wide state of libamphion_hip.so: error text, the kernel log and launch manifest, the f16 operand-range guard, the default
+// precision, the launch-policy Config with its amp_set_* switches, and device_upload.
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <string>
+
+#include "amp_host.h"
+
+namespace amp {
+
+// ------------------------------------------------------------------------------------------------
+// errors
+// ------------------------------------------------------------------------------------------------
+static thread_local char g_err[512] = "";
+
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+
+// ---- f16 operand-range guard (amp_host.h: RangeGuard) ------------------------------------------------------------
+static RangeGuard g_guard[64];                    // op-level launches (amp_conv_forward, amp_pair_forward, ...): one word per device
+__thread std::string* tl_kernel_log = nullptr;    // amp_internal.h: note_kernel()
+__thread char tl_last_kernel[160] = "";
+// launch manifest (amp_internal.h): AMP_LAUNCH_MANIFEST=<file>, read once; lines are appended and flushed per launch (profiling runs only)
+static FILE* manifest_file() {
+    static FILE* f = [] {
+        const char* p = getenv("AMP_LAUNCH_MANIFEST");
+        return (p && *p) ? fopen(p, "a") : nullptr;
+    }();
+    return f;
+}
+bool manifest_on() {
+    static const bool on = manifest_file() != nullptr;
+    return on;
+}
+void manifest_add(const char* name, unsigned long long workgroups, double gflop, double mb, const char* what) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    FILE* f = manifest_file();
+    if (!f) return;
+    fprintf(f, "%s\t%llu\t%.6f\t%.6f\t%s\n", name, workgroups, gflop, mb, what);
+    fflush(f);
+    tl_last_kernel[0] = '\0';   // a launcher that forgets note_kernel() shows up as an EMPTY name, not as the previous kernel's
+}
+static thread_local unsigned* tl_range_flag = nullptr;   // set while an amp_gen forward is launching: that handle's own word
+RangeFlagScope::RangeFlagScope(unsigned* word) { tl_range_flag = word; }
+RangeFlagScope::~RangeFlagScope() { tl_range_flag = nullptr; }
+
+bool guard_init(RangeGuard& g) {
+    if (g.dev) return true;
+    if (hipMalloc(&g.dev, sizeof(unsigned)) != hipSuccess) { g.dev = nullptr; return false; }
+    if (hipMemset(g.dev, 0, sizeof(unsigned)) != hipSuccess || hipHostMalloc(&g.host, sizeof(unsigned)) != hipSuccess ||
+        hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipFree(g.dev);
+        g.dev = nullptr;
+        return false;
+    }
+    *g.host = 0;
+    return true;
+}
+
+void guard_free(RangeGuard& g) {
+    if (g.dev) (void)hipFree(g.dev);
+    if (g.host) (void)hipHostFree(g.host);
+    if (g.ev) (void)hipEventDestroy(g.ev);
+    g = RangeGuard{};
+}
+
+static RangeGuard* guard_for_current_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    return guard_init(g_guard[dev]) ? &g_guard[dev] : nullptr;
+}
+
+// the word the f16x3 kernels of the launch being set up report to
+unsigned* range_flag_for_current_device() {
+    if (tl_range_flag) return tl_range_flag;
+    RangeGuard* g = guard_for_current_device();
+    return g ? g->dev : nullptr;
+}
+
+static bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+static const char kRangeMsg[] =
+    "an activation left the split-f16 operand range of the f16x3 kernels (|x| > 4094 or infinite) in a previous "
+    "launch: its output is not the fp32 reference's; re-run with amp_set_precision(AMP_PRECISION_F32)";
+
+int range_poll(RangeGuard* g, hipStream_t st) {
+    if (!g || !g->dev || !g->pending || stream_is_capturing(st)) return AMP_OK;
+    if (hipEventQuery(g->ev) != hipSuccess) return AMP_OK;       // still in flight
+    g->pending = false;
+    if (*g->host == 0) return AMP_OK;
+    *g->host = 0;
+    AMP_HIP(hipMemsetAsync(g->dev, 0, sizeof(unsigned), st));
+    set_error("%s", kRangeMsg);
+    return AMP_ERR_RANGE;
+}
+
+int range_publish(RangeGuard* g, hipStream_t st) {
+    if (!g || !g->dev || stream_is_capturing(st)) return AMP_OK;
+    AMP_HIP(hipMemcpyAsync(g->host, g->dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipEventRecord(g->ev, st));
+    g->pending = true;
+    return AMP_OK;
+}
+
+int range_check_sync(RangeGuard* g, hipStream_t st, const char* who) {
+    if (!g || !g->dev) return AMP_OK;
+    if (stream_is_capturing(st)) { set_error("%s: the stream is capturing", who); return AMP_ERR_STATE; }
+    // copy into the pinned mirror (a pageable destination would make the copy itself a second, staged wait), then ONE blocking
+    // wait: the thread sleeps until the stream drains -- it must not spin, CPU time is what a container's quota meters
+    // (profiles/r3_o_list_api_cgroup_throttle.txt: the list API's 37 / 60 ms alternation was the host being throttled)
+    AMP_HIP(hipMemcpyAsync(g->host, g->dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    AMP_HIP(hipStreamSynchronize(st));
+    g->pending = false;
+    const unsigned v = *g->host;
+    *g->host = 0;
+    if (v == 0) return AMP_OK;
+    AMP_HIP(hipMemsetAsync(g->dev, 0, sizeof(unsigned), st));
+    set_error("%s", kRangeMsg);
+    return AMP_ERR_RANGE;
+}
+
+// Process-wide default for handles created from now on: AMP_PRECISION=f32|f16x3, amp_set_precision().
+static int g_precision = -1;
+int default_precision() {
+    if (g_precision < 0) {
+        const char* e = getenv("AMP_PRECISION");
+        g_precision = (e && (!strcmp(e, "f32") || !strcmp(e, "fp32"))) ? PREC_F32 : PREC_F16X3;
+    }
+    return g_precision;
+}
+
+// ---- launch-policy switches (amp_host.h: Config) ------------------------------------------------------------
+Config::Config() {
+    auto num = [](const char* name, int lo, int hi, int dflt) {
+        const char* e = getenv(name);
+        if (!e || !*e) return dflt;
+        const int v = atoi(e);
+        return (v < lo || v > hi) ? dflt : v;
+    };
+    rb_fusion = num("AMP_RB_FUSION", 0, 3, 1);
+    ampb_fusion = num("AMP_AMPB_FUSION", 0, 3, 1);
+    rb_streams = num("AMP_RB_STREAMS", -1, 1, -1);
+    // a deployment that still sets one of the switches round 5 removed must hear about it -- once, here (AMP_GROUP_MB bounded the
+    // generator workspace: 168 MB instead of 2.7 GB at config 2; without a word the full-size workspace comes back after an upgrade)
+    static const char* const kRemoved[][2] = {
+        {"AMP_GROUP_MB", "amp_set_group_mb(megabytes)"}, {"AMP_PAIR_STRIP", "amp_set_pair_strips(mode)"}, {"AMP_CONV_BLK", "amp_set_conv_blk(mode)"},
+        {"AMP_FUSE_PAIRS", "nothing (the fused pairs are the only form)"}, {"AMP_RB_SUM_FRAMES", "nothing"},
+        {"AMP_RB_HORIZONTAL", "amp_set_resblock_streams(mode)"}, {"AMP_RB_HORIZONTAL_FRAMES", "amp_set_resblock_streams(mode)"}};
+    for (const auto& r : kRemoved) {
+        const char* e = getenv(r[0]);
+        if (e && *e) fprintf(stderr, "libamphion_hip: the environment variable %s=%s is no longer read (removed in ABI 142); use %s\n", r[0], e, r[1]);
+    }
+}
+Config& cfg() { static Config c; return c; }
+
+int device_upload(const void* host, size_t bytes, void** out) {
+    void* p = nullptr;
+    AMP_HIP(hipMalloc(&p, bytes));
+    const hipError_t e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        set_error("hipMemcpy of %zu bytes to the device failed: %s", bytes, hipGetErrorString(e));
+        return AMP_ERR_HIP;
+    }
+    *out = p;
+    return AMP_OK;
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+// 100: round 1; 120: + amp_conv_create_gated / amp_wn_forward / amp_conv_act_forward, switches; 122: + amp_set_conv_blk / _conv_rg_fast /
+// _pingpong; 130 (round 3's ABI, numbered in round 4): amp_mel_desc grew four trailing fields, + amp_resblock_forward /
+// amp_set_resblock_fusion / amp_gen_kernel_name; 140: amp_mel_desc.struct_size, + amp_ampblock_forward / amp_set_ampblock_fusion / amp_mel_init;
+// 141 (additive): the ragged / fused entry points of the VITS text side (amp_conv_forward_ragged, amp_layer_norm_c_ragged, amp_dwconv_layer_norm_c,
+// amp_rel_attention_strided, amp_set_rel_attention_tiled, amp_expand_path_strided); 142 (round 5, REMOVALS): amp_conv_act_forward, amp_set_fuse_act,
+// amp_set_wn_layer_fusion are gone with the kernels behind them (never chosen by the launch policy), amp_set_pair_strips(1) is refused; amp_mel_forward
+// accepts every n_fft in [64, 4096]; 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision / amp_pw_destroy and
+// amp_istft_same_polar, amp_dwconv_layer_norm_c takes K = 7; 144 (additive): the DiffWave entry points amp_dw_* (diffwave.hip)
+int amp_version(void) { return 144; }
+const char* amp_last_error(void) { return g_err; }
+
+int amp_set_precision(int precision) {
+    if (precision != AMP_PRECISION_F32 && precision != AMP_PRECISION_F16X3) {
+        set_error("amp_set_precision: unknown precision %d", precision);
+        return AMP_ERR_INVALID;
+    }
+    g_precision = precision;
+    return AMP_OK;
+}
+
+int amp_get_precision(void) { return default_precision(); }
+
+int amp_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int amp_set_pair_strips(int on) {
+    if (on < -1 || on > 0) { set_error("amp_set_pair_strips: %d (-1 the policy, 0 the per-tile kernel everywhere; the four-wave strips of mode 1 left in ABI 142)", on); return AMP_ERR_INVALID; }
+    cfg().pair_strips = on;
+    return AMP_OK;
+}
+
+int amp_set_group_mb(int megabytes) {
+    if (megabytes < 0) { set_error("amp_set_group_mb: %d", megabytes); return AMP_ERR_INVALID; }
+    cfg().group_bytes = (size_t)megabytes << 20;
+    return AMP_OK;
+}
+
+int amp_set_resblock_streams(int mode) {
+    if (mode < -1 || mode > 1) { set_error("amp_set_resblock_streams: mode=%d", mode); return AMP_ERR_INVALID; }
+    cfg().rb_streams = mode;
+    return AMP_OK;
+}
+
+int amp_set_small_conv(int on) {
+    cfg().small_conv = on ? 1 : 0;
+    return AMP_OK;
+}
+
+int amp_set_pingpong(int on) {
+    cfg().pingpong = on < 0 ? kPingPongDefault : (on ? 1 : 0);   // -1: back to the default
+    return AMP_OK;
+}
+
+int amp_set_conv_rg_fast(int on) {
+    cfg().conv_rg_fast = on < 0 ? kConvRgFastDefault : (on ? 1 : 0);   // -1: back to the default
+    return AMP_OK;
+}
+
+int amp_set_conv_blk_narrow(int on) {
+    if (on < -1 || on > 2) { set_error("amp_set_conv_blk_narrow: %d (0 off, 1 policy: 128-row convs with k >= 7, 2 every 128-row conv, -1 default)", on); return AMP_ERR_INVALID; }
+    cfg().narrow_blk = on < 0 ? 1 : on;
+    return AMP_OK;
+}
+
+int amp_set_conv_blk(int mode) {
+    if (mode < -1 || mode > 3) { set_error("amp_set_conv_blk: mode %d (0 off, 1 | 2 chunks per staging round, 3 = 2 + k = 7 / 11, -1 default)", mode); return AMP_ERR_INVALID; }
+    cfg().conv_blk = mode < 0 ? kConvBlkDefault : mode;
+    return AMP_OK;
+}
+
+int amp_set_resblock_fusion(int mode) {
+    if (mode < -1 || mode > 3) { set_error("amp_set_resblock_fusion: mode=%d", mode); return AMP_ERR_INVALID; }
+    cfg().rb_fusion = mode < 0 ? 1 : mode;
+    return AMP_OK;
+}
+
+int amp_set_ampblock_fusion(int mode) {
+    if (mode < -1 || mode > 3) { set_error("amp_set_ampblock_fusion: mode=%d", mode); return AMP_ERR_INVALID; }
+    cfg().ampb_fusion = mode < 0 ? 1 : mode;
+    return AMP_OK;
+}
+
+int amp_range_check(void* stream_) {
+    return range_check_sync(guard_for_current_device(), (hipStream_t)stream_, "amp_range_check");
+}
+
+}  // extern "C"

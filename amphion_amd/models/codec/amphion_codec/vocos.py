@@ -21,7 +21,6 @@ Not on the HIP path (``NotImplementedError``): ``padding="center"`` and AdaLayer
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Optional
 
 import numpy as np
@@ -29,21 +28,11 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._lib import ptr as _p
 from amphion_amd.modules.hip_ops import HipConv1d
 
 MAG_CLIP = 1e2          # ISTFTHead: torch.clip(exp(mag), max=1e2) (vocos.py:349-352)
 LN_EPS = 1e-6
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _destroy_pw(ptr):
-    try:
-        _lib.lib().amp_pw_destroy(ctypes.c_void_p(ptr))
-    except Exception:
-        pass
 
 
 class _PwHandle:
@@ -65,7 +54,7 @@ class _PwHandle:
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_pw_create(lin.in_features, lin.out_features, _p(w), _p(b), ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, weakref.finalize(self, _destroy_pw, h.value)
+        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_pw_destroy", h)
         return h
 
 

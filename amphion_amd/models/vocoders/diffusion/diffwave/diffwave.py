@@ -16,7 +16,6 @@ the op-level f16x3 range flag is checked (``_lib.range_check``): an activation b
 from __future__ import annotations
 
 import ctypes
-import weakref
 from math import sqrt  # noqa: F401  (the reference module exports it)
 
 import numpy as np
@@ -24,17 +23,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _destroy(ptr):
-    try:
-        _lib.lib().amp_dw_destroy(ctypes.c_void_p(ptr))
-    except Exception:
-        pass
+from amphion_amd._lib import ptr as _p
 
 
 def Conv1d(*args, **kwargs):
@@ -128,7 +117,7 @@ class DiffWave(nn.Module):
         L = _lib.lib()
         with torch.cuda.device(device):
             _lib.check(L.amp_dw_create(ctypes.byref(d), ctypes.byref(h)))
-            fin = weakref.finalize(self, _destroy, h.value)
+            fin = _lib.finalizer(self, "amp_dw_destroy", h)
             try:
                 for k, t in tensors:
                     w = t.detach().to("cpu", torch.float32).contiguous()

@@ -109,13 +109,6 @@ class ConvParams(nn.Module):
                f"padding={self.padding}, weight_norm={self.has_weight_norm})"
 
 
-def _destroy_handle(ptr):
-    try:
-        _lib.lib().amp_gen_destroy(ctypes.c_void_p(ptr))
-    except Exception:  # interpreter shutdown
-        pass
-
-
 class _InferenceOnly(torch.autograd.Function):
     """Identity on the generator's output whose backward raises: see ``HipGenerator._amp_forward``."""
 
@@ -234,7 +227,7 @@ class HipGenerator(nn.Module):
         desc = self._amp_desc()
         h = ctypes.c_void_p()
         _lib.check(L.amp_gen_create(ctypes.byref(desc), ctypes.byref(h)))
-        fin = weakref.finalize(self, _destroy_handle, h.value)
+        fin = _lib.finalizer(self, "amp_gen_destroy", h)
         prev_prec = L.amp_get_precision()
         try:
             staged = []

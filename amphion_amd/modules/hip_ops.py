@@ -2,23 +2,12 @@
 from __future__ import annotations
 
 import ctypes
-import weakref
 
 import torch
 
 from amphion_amd import _lib
+from amphion_amd._lib import ptr as _ptr
 from amphion_amd.models.vocoders.gan.generator._engine import ConvParams
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _destroy_conv(ptr):
-    try:
-        _lib.lib().amp_conv_destroy(ctypes.c_void_p(ptr))
-    except Exception:
-        pass
 
 
 class HipConv1d(ConvParams):
@@ -57,7 +46,7 @@ class HipConv1d(ConvParams):
                 _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_PAD_REFLECT, 1))
             if self.tanh:
                 _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_TANH, 1))
-        self._h, self._fin, self._sig = h, weakref.finalize(self, _destroy_conv, h.value), sig
+        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
         self._prec = _lib.get_precision()      # a handle keeps the arithmetic it was built with (amphion_hip.h)
         return h
 
@@ -79,7 +68,7 @@ class HipConv1d(ConvParams):
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create_gated(self.cin, self.k, self.dilation, self.padding, _ptr(w), _ptr(b), ctypes.byref(h)))
-        self._hg, self._fin_g = h, weakref.finalize(self, _destroy_conv, h.value)
+        self._hg, self._fin_g = h, _lib.finalizer(self, "amp_conv_destroy", h)
         return h
 
     def forward(self, x, *, slope_in=1.0, res=None, slope_out=1.0, out=None, x_batch_stride=None, T=None, lens=None):
@@ -140,7 +129,7 @@ class MergedConv1d:
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create(0, c0.cin, w.shape[0], c0.k, c0.stride, c0.dilation, c0.padding, _ptr(w), _ptr(b),
                                                   ctypes.byref(h)))
-        self._h, self._fin, self._sig = h, weakref.finalize(self, _destroy_conv, h.value), sig
+        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
         return h
 
     def __call__(self, convs, x, lens=None):

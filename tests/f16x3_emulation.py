@@ -2,7 +2,7 @@
 
 The kernels stage an activation as hi + lo f16 after an exact x16 (f16x3_device.h: split_f16, stage4_f16; leaky ReLU on load is
 max(16 x, 16 slope x)), pack each weight as hi + lo f16 after a power-of-two scale that puts max|w| in (2^12, 2^13]
-(generator.hip: conv_build), and accumulate three MFMA products in fp32: W_hi X_hi + W_hi X_lo + W_lo X_hi.  W_lo X_lo is dropped.
+(amp_host.h: pow2_weight_scale, pack_a_f16x3), and accumulate three MFMA products in fp32: W_hi X_hi + W_hi X_lo + W_lo X_hi.  W_lo X_lo is dropped.
 Each f16 x f16 product is exact in fp32, so fp32 convolutions of the hi / lo parts emulate the products exactly and the
 accumulation's rounding roughly (the order of the sums differs from the MFMA's).
 

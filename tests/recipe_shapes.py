@@ -2,13 +2,13 @@
 
 Recipes (oracle/vocoder_oracle.py): bigvgan_large_hp, tfr_hifigan_hp, nsfhifigan_recipe_hp and hifigan_recipe_hp (resblock "2").
 Every layer is listed once with the recipes it occurs in: conv_pre, every ConvTranspose1d, every resblock conv (C, k, dilation) and
-every conv_post.  `form()` restates conv_run's choice (amphion_amd/csrc/generator.hip) so that each case can be sized to reach the
+every conv_post.  `form()` restates conv_run's choice (amphion_amd/csrc/conv_host.hip) so that each case can be sized to reach the
 kernel it names; the tests assert the kernel from the launch manifest, so a restatement that drifts from the library fails loudly.
 """
 from dataclasses import dataclass
 
 N_MEL = {"bigvgan_large": 100, "tfr": 100, "nsf": 100, "hifigan_rb2": 80}
-TAPS = (1, 2, 3, 5, 7, 11)                       # generator.hip: ConvTaps
+TAPS = (1, 2, 3, 5, 7, 11)                       # conv_host.hip: ConvTaps
 SMALL_GRID_WGS = 384                             # kSmallGridWorkgroups
 BLK_MIN_WGS = 512                                # kConvBlkMinWorkgroups
 RG_FAST_MAX_BYTES = 3 << 20                      # kConvRgFastMaxWeightBytes
@@ -54,7 +54,7 @@ class Op:
             return (T - 1) * self.u - 2 * self.padding + self.k
         return T + 2 * self.padding - self.d * (self.k - 1)
 
-    # ---- the GEMM view (generator.hip: conv_build) ----
+    # ---- the GEMM view (conv_host.hip: conv_build) ----
     @property
     def M(self):
         return self.cout * (self.u or 1)

@@ -53,7 +53,7 @@ RING_CASES = [
     (128, 11, 5, 64, 2100),
     (128, 7, 3, 64, 4100),
     (128, 11, 1, 48, 6000),
-    # 1 024+ four-step strips (round 5: generator.hip strip_geometry): the headline's stage shape, and one whose last strip is a ragged tail
+    # 1 024+ four-step strips (round 5: conv_host.hip strip_geometry): the headline's stage shape, and one whose last strip is a ragged tail
     (128, 11, 3, 64, 16384),
     (128, 7, 1, 70, 15000),
 ]

@@ -156,7 +156,7 @@ def test_generator_with_resblock_kernel_equals_pairs(mode, fusion):
 
 
 def test_low_yield_resblock_runs_as_two_launches_with_the_same_bits(fusion, tmp_path):
-    """Round 5 (generator.hip rb_split): a whole-resblock tile that keeps less than 80 % of its columns (C = 64, k = 11: 392 of 512) runs as pairs
+    """Round 5 (conv_host.hip rb_split): a whole-resblock tile that keeps less than 80 % of its columns (C = 64, k = 11: 392 of 512) runs as pairs
     [0, 2) + [2, 3) once the launch has 1 024+ workgroups.  Same bits as the fused pairs (dense and ragged), and the launch manifest shows the
     two launches (4 convs, then 2 convs with the MRF sum) where a smaller batch shows one (6 convs)."""
     import os, subprocess, sys

@@ -160,7 +160,7 @@ def test_bound_separates_three_from_two_terms():
 
 
 def test_emulation_weight_scale_matches_the_packing():
-    """generator.hip conv_build: max|w| * 2^s in (2^12, 2^13], a power of two max|w| lands on 2^13 exactly"""
+    """amp_host.h pow2_weight_scale: max|w| * 2^s in (2^12, 2^13], a power of two max|w| lands on 2^13 exactly"""
     for m in (1.0, 0.75, 3.0, 2.0 ** -7, 1e-3):
         s = emu.weight_scale(torch.tensor([m, -m / 3]))
         assert 2.0 ** 12 < m * s <= 2.0 ** 13, m

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A whole ResBlock1 in one rb_f16x3 launch against the same resblock as 2 + 1, 1 + 2 and 1 + 1 + 1 pairs per launch (op-level C ABI,
 amp_resblock_forward on sub-lists of the conv handles; each variant looped for ~2 s so that the package sits at its power cap as it does in
-the forward).  Behind generator.hip's rb_split() policy: profiles/r5_l_rb_split.txt.  Tuning aid; not part of the product."""
+the forward).  Behind conv_host.hip's rb_split() policy: profiles/r5_l_rb_split.txt.  Tuning aid; not part of the product."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
