@@ -334,11 +334,16 @@ inline void note_work(unsigned long long workgroups, double gflop, double mb, co
 // a Conv1d / ConvTranspose1d launch: GEMM M = Cout * up rows, K = Cin * KT, N = B * Tq columns; bytes = x read once + y written once
 // (+ the residual / running sum read).  `grid=XxY` states the launch's grid: Y > 1 is the 2-D order (row group = blockIdx.y), Y = 1 with
 // several row groups the row-group-fastest 1-D order (ConvArgs::row_groups)
+// The label follows the HANDLE (tl_conv_transposed, set by conv_run for the launch it issues next), not a.up: a stride-1
+// ConvTranspose1d runs as the equivalent Conv1d (conv_build) and is still a "ConvT".
+extern __thread int tl_conv_transposed;
 inline void note_conv_work(const ConvArgs& a, int KT, dim3 grid) {
+    const bool convt = tl_conv_transposed != 0;
+    tl_conv_transposed = 0;
     if (!manifest_on()) return;
     const double gf = 2.0 * a.M * a.Cin * KT * (double)a.Tq * a.B / 1e9;
     const double mb = 4.0 * a.B * ((double)a.Cin * a.Tin + (double)a.Cout * a.Tout * (1 + (a.res ? 1 : 0) + (a.mode ? 1 : 0))) / 1e6;
-    note_work((unsigned long long)grid.x * grid.y, gf, mb, "%s %d->%d k=%d d=%d T=%d->%d B=%d%s%s grid=%ux%u", a.up > 1 ? "ConvT" : "conv", a.Cin,
+    note_work((unsigned long long)grid.x * grid.y, gf, mb, "%s %d->%d k=%d d=%d T=%d->%d B=%d%s%s grid=%ux%u", convt ? "ConvT" : "conv", a.Cin,
               a.Cout, a.up > 1 ? KT * a.up : KT, a.dstep, a.Tin, a.Tout, a.B, a.res ? " +res" : "", a.mode ? " +sum" : "", grid.x, grid.y);
 }
 

@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
             for (int t = 0; t < NI; ++t) {
                 const int q = qw + 32 * t;
                 const int n0 = q * up + ph - a.up_pad;
-                if (q < a.Tq && n0 >= 0 && n0 + 3 < a.Tout) {
+                if (q < a.Tq && n0 >= 0 && n0 < a.Tout) {
                     float4 v;
                     v.x = acc[t][4 * j + 0] * a.inv_scale;
                     v.y = acc[t][4 * j + 1] * a.inv_scale;
@@ -303,7 +303,13 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
                     v.y = v.y > 0.f ? v.y : v.y * slope_out;
                     v.z = v.z > 0.f ? v.z : v.z * slope_out;
                     v.w = v.w > 0.f ? v.w : v.w * slope_out;
-                    *reinterpret_cast<float4*>(yrow + n0) = v;
+                    if (n0 + 3 < a.Tout) {
+                        *reinterpret_cast<float4*>(yrow + n0) = v;
+                    } else {   // the quad that crosses the row's end (Tout = k mod 4 here): per-sample stores
+                        yrow[n0] = v.x;
+                        if (n0 + 1 < a.Tout) yrow[n0 + 1] = v.y;
+                        if (n0 + 2 < a.Tout) yrow[n0 + 2] = v.z;
+                    }
                 }
             }
         }

@@ -192,8 +192,18 @@ int conv_build(amp_conv* c, const float* w, const float* bias) {
         c->ntaps = c->k;
         c->off0 = -c->padding;     // y[t] = sum_j w[j] x[t - pad + j*dil]
         c->dstep = c->dilation;
+    } else if (c->stride == 1) {
+        // ConvTranspose1d(stride 1, padding p) IS the Conv1d with flipped taps and padding k - 1 - p (wview below): no polyphase rows, and
+        // the kernels' up == 1 store paths (which write column q unshifted) are right for it.  c->transposed stays set: out_len, the
+        // option / ragged refusals and the manifest label follow the handle.
+        if (c->dilation != 1) { set_error("amp_conv: dilated ConvTranspose1d unsupported (dilation=%d)", c->dilation); return AMP_ERR_UNSUPPORTED; }
+        c->up = 1; c->up_pad = 0;
+        c->M = c->cout;
+        c->ntaps = c->k;
+        c->off0 = -(c->k - 1 - c->padding);
+        c->dstep = 1;
     } else {
-        if (c->dilation != 1) { set_error("amp_conv: dilated ConvTranspose1d unsupported"); return AMP_ERR_UNSUPPORTED; }
+        if (c->dilation != 1) { set_error("amp_conv: dilated ConvTranspose1d unsupported (dilation=%d)", c->dilation); return AMP_ERR_UNSUPPORTED; }
         c->up = c->stride; c->up_pad = c->padding;
         c->M = c->cout * c->stride;
         c->ntaps = (c->k + c->stride - 1) / c->stride;
@@ -201,13 +211,14 @@ int conv_build(amp_conv* c, const float* w, const float* bias) {
         c->dstep = -1;             // tap s reads x[q - s]
     }
     c->KT = round_up_taps(c->ntaps);
-    if (c->KT < 0) { set_error("amp_conv: %d taps unsupported (max 11)", c->ntaps); return AMP_ERR_UNSUPPORTED; }
+    if (c->KT < 0) { set_error("amp_conv: k=%d at stride=%d is %d taps, unsupported (max 11)", c->k, c->stride, c->ntaps); return AMP_ERR_UNSUPPORTED; }
     const int omin = c->dstep >= 0 ? c->off0 : c->off0 + (c->KT - 1) * c->dstep;
     const int omax = c->dstep >= 0 ? c->off0 + (c->KT - 1) * c->dstep : c->off0;
     c->halo_left = omin < 0 ? -omin : 0;
     c->halo_right = omax > 0 ? omax : 0;
     if (!choose_plan(c->KT, c->M, c->halo_left + c->halo_right, 0, &c->plan)) {
-        set_error("amp_conv: receptive field (k=%d, dilation=%d) exceeds the 128-column staged halo", c->k, c->dilation);
+        set_error("amp_conv: receptive field (k=%d, dilation=%d, padding=%d: %d columns) exceeds the 128-column staged halo", c->k, c->dilation,
+                  c->padding, c->halo_left + c->halo_right);
         return AMP_ERR_UNSUPPORTED;
     }
     c->precision = default_precision();
@@ -221,6 +232,7 @@ int conv_build(amp_conv* c, const float* w, const float* bias) {
     auto wview = [&](int m, int i, int g) -> float {
         if (m >= c->M || i >= cin || g >= c->ntaps) return 0.f;
         if (!c->transposed) return w[((size_t)m * cin + i) * k + g];
+        if (up == 1) return w[((size_t)i * cout + m) * k + (k - 1 - g)];   // stride 1: the flipped taps of the equivalent Conv1d
         const int o = m / up, r = m - o * up;
         const int j = r + g * up;
         return j < k ? w[((size_t)i * cout + o) * k + j] : 0.f;
@@ -279,11 +291,11 @@ int conv_run(const amp_conv* c, const float* x, int B, int T, float slope_in, co
              ConvArgs* plan_small, int* plan_ni) {
     if (B <= 0 || T <= 0) { set_error("amp_conv_forward: B=%d T=%d", B, T); return AMP_ERR_INVALID; }
     const int Tout = conv_out_len(c, T);
-    if (Tout <= 0) { set_error("amp_conv_forward: input too short (T=%d)", T); return AMP_ERR_INVALID; }
+    if (Tout <= 0) { set_error("amp_conv_forward: input too short (T=%d gives T_out=%d)", T, Tout); return AMP_ERR_INVALID; }
     ConvArgs a{};
     a.x = x; a.wp = c->wp_dev; a.bias = c->bias_dev; a.res = res; a.y = y;
     a.B = B; a.Cin = c->cin; a.Tin = T; a.xbs = xbs > 0 ? xbs : (long long)c->cin * T; a.nchunks = c->nchunks; a.M = c->M;
-    a.Tq = c->transposed ? T + c->ntaps - 1 : Tout;
+    a.Tq = c->up > 1 ? T + c->ntaps - 1 : Tout;   // polyphase: every input column and the taps' tail; else one GEMM column per output
     ConvPlan plan = c->plan;
     if (c->precision == PREC_F16X3) {
         // a grid that leaves most CUs idle (a single utterance): half-width tiles, twice the workgroups
@@ -310,6 +322,7 @@ int conv_run(const amp_conv* c, const float* x, int B, int T, float slope_in, co
         set_error("amp_conv_forward: leaky_relu slope %g > 1 on the input is outside the f16x3 kernels (use AMP_PRECISION_F32)", (double)slope_in);
         return AMP_ERR_UNSUPPORTED;
     }
+    tl_conv_transposed = c->transposed;           // the manifest label of the launch below (amp_internal.h: note_conv_work)
     if (c->precision == PREC_F32) {
         if (plan_small) return AMP_ERR_UNSUPPORTED;
         a.acc_scale = a.inv_scale = 1.f;

@@ -28,6 +28,7 @@ void set_error(const char* fmt, ...) {
 static RangeGuard g_guard[64];                    // op-level launches (amp_conv_forward, amp_pair_forward, ...): one word per device
 __thread std::string* tl_kernel_log = nullptr;    // amp_internal.h: note_kernel()
 __thread char tl_last_kernel[160] = "";
+__thread int tl_conv_transposed = 0;              // amp_internal.h: note_conv_work()
 // launch manifest (amp_internal.h): AMP_LAUNCH_MANIFEST=<file>, read once; lines are appended and flushed per launch (profiling runs only)
 static FILE* manifest_file() {
     static FILE* f = [] {

@@ -189,7 +189,13 @@ typedef struct amp_conv amp_conv;
 
 /* One Conv1d (nn.Conv1d(cin, cout, k, 1, dilation=d, padding=get_padding(k, d)), gan_utils.py:12) or
  * ConvTranspose1d(cin, cout, k, stride, padding) (hifigan.py:176-186).  weight_host is the FOLDED
- * weight: [cout, cin, k] for a conv, [cin, cout, k] for a transposed conv.  bias_host may be NULL. */
+ * weight: [cout, cin, k] for a conv, [cin, cout, k] for a transposed conv.  bias_host may be NULL.
+ * Geometry (tests/test_gpu_conv_geometry.py runs all of it against fp64): Conv1d with stride 1, any k, dilation and padding >= 0 whose
+ * staged receptive field max(0, p) + max(0, (kt - 1) * dilation - p) is at most 128 columns (kt = k rounded up to 1, 2, 3, 5, 7, 11;
+ * k <= 11); ConvTranspose1d with dilation 1, any stride >= 1, any k with ceil(k / stride) <= 11 (k < stride included) and any
+ * padding >= 0 (stride 1 runs as the equivalent Conv1d).  Refused here with AMP_ERR_UNSUPPORTED: a strided Conv1d, a dilated
+ * ConvTranspose1d, more than 11 taps, a receptive field beyond the halo.  Refused by the forward calls with AMP_ERR_INVALID: a T whose
+ * T_out (amp_conv_out_len) is <= 0. */
 int amp_conv_create(int transposed, int cin, int cout, int k, int stride, int dilation, int padding,
                     const float* weight_host, const float* bias_host, amp_conv** out);
 int amp_conv_out_len(const amp_conv* c, int T);

@@ -58,14 +58,18 @@ def conv_window(x, w, b=None, *, rows, windows, items=None, transposed=False, st
             # y[t] = sum over i * stride - padding + j = t of x[i] w[i, :, j]: inputs i in [ceil((t0 + p - k + 1) / s), floor((t1 - 1 + p) / s)]
             i0 = max(0, -((k - 1 - t0 - padding) // stride))
             i1 = min(T - 1, (t1 - 1 + padding) // stride)
-            sl = xs[:, :, i0: i1 + 1]
-            base = i0 * stride - padding                      # global column of the slice's local output 0
-            r = F.conv_transpose1d(sl, wr, stride=stride)
-            c = F.conv_transpose1d(sl.abs(), wr.abs(), stride=stride)
-            need = t1 - base
-            if r.shape[-1] < need:
-                r, c = F.pad(r, (0, need - r.shape[-1])), F.pad(c, (0, need - c.shape[-1]))
-            r, c = r[:, :, t0 - base:], c[:, :, t0 - base:]
+            r = torch.zeros(len(items), len(rows), t1 - t0, dtype=torch.float64)
+            c = torch.zeros_like(r)
+            if i1 >= i0:                                      # else no input reaches the window (k < stride): bias + residual only
+                sl = xs[:, :, i0: i1 + 1]
+                base = i0 * stride - padding                  # global column of the slice's local output 0
+                rs = F.conv_transpose1d(sl, wr, stride=stride)
+                cs = F.conv_transpose1d(sl.abs(), wr.abs(), stride=stride)
+                # the slice's outputs cover [base, base + len): with k < stride that may start after t0 or end before t1
+                g0, g1 = max(t0, base), min(t1, base + rs.shape[-1])
+                if g1 > g0:
+                    r[:, :, g0 - t0: g1 - t0] = rs[:, :, g0 - base: g1 - base]
+                    c[:, :, g0 - t0: g1 - t0] = cs[:, :, g0 - base: g1 - base]
         refs.append(r[:, :, : t1 - t0])
         conds.append(c[:, :, : t1 - t0])
         cols.append(torch.arange(t0, t1))
@@ -77,6 +81,29 @@ def conv_window(x, w, b=None, *, rows, windows, items=None, transposed=False, st
         rr = res[items][:, rows][:, :, cols].double()
         ref, cond = ref + rr, cond + rr.abs()
     return _lrelu(ref, slope_out), cond, cols
+
+
+def conv_full(x, w, b=None, *, transposed=False, stride=1, dilation=1, padding=0, slope_in=1.0, res=None, slope_out=1.0, reflect=False,
+              tanh=False):
+    """fp64 (ref, cond) of the WHOLE output, straight from torch's conv: what conv_window is pinned to (tests/test_conv_geometry_ref.py)
+    and the reference of the small-grid geometry cases.  reflect: the padding mirrors (nn.ReflectionPad1d + unpadded conv); tanh: on the
+    output (cond stays that of the sum: |tanh(a) - tanh(b)| <= |a - b|)."""
+    xa = _lrelu(x.double(), slope_in)
+    wd = w.double()
+    if transposed:
+        r = F.conv_transpose1d(xa, wd, stride=stride, padding=padding)
+        c = F.conv_transpose1d(xa.abs(), wd.abs(), stride=stride, padding=padding)
+    else:
+        if reflect:
+            xa, padding = F.pad(xa, (padding, padding), mode="reflect"), 0
+        r = F.conv1d(xa, wd, dilation=dilation, padding=padding)
+        c = F.conv1d(xa.abs(), wd.abs(), dilation=dilation, padding=padding)
+    if b is not None:
+        r, c = r + b.double().view(1, -1, 1), c + b.double().abs().view(1, -1, 1)
+    if res is not None:
+        r, c = r + res.double(), c + res.double().abs()
+    r = _lrelu(r, slope_out)
+    return (torch.tanh(r) if tanh else r), c
 
 
 def pick(y, items, rows, cols):

@@ -7,8 +7,9 @@ from amphion_amd import _lib
 
 
 def conv_forward(w, b, x, *, transposed=False, stride=1, dilation=1, padding=0, slope_in=1.0, res=None,
-                 slope_out=1.0):
-    """Run amp_conv_* on cuda:0.  w/b are CPU tensors (folded weight), x a CPU tensor [B, Cin, T]."""
+                 slope_out=1.0, options=()):
+    """Run amp_conv_* on cuda:0.  w/b are CPU tensors (folded weight), x a CPU tensor [B, Cin, T].
+    options: (amp_conv_option, value) pairs for amp_conv_set_option, applied to the new handle before the forward."""
     L = _lib.lib()
     h = ctypes.c_void_p()
     w = w.contiguous().float()
@@ -18,10 +19,13 @@ def conv_forward(w, b, x, *, transposed=False, stride=1, dilation=1, padding=0, 
     _lib.check(L.amp_conv_create(int(transposed), cin, cout, w.shape[2], stride, dilation, padding,
                                  ctypes.c_void_p(w.data_ptr()), bptr, ctypes.byref(h)))
     try:
+        for option, value in options:
+            _lib.check(L.amp_conv_set_option(h, int(option), int(value)))
         xd = x.contiguous().float().cuda()
         B, _, T = xd.shape
         Tout = L.amp_conv_out_len(h, T)
-        y = torch.full((B, cout, Tout), float("nan"), device="cuda")
+        # (T_out <= 0 is the library's to refuse: amp_conv_forward still gets a real pointer)
+        y = torch.full((B, cout, Tout if Tout > 0 else 1), float("nan"), device="cuda")
         rd = res.contiguous().float().cuda() if res is not None else None
         _lib.check(L.amp_conv_forward(h, ctypes.c_void_p(xd.data_ptr()), B, T, slope_in,
                                       ctypes.c_void_p(rd.data_ptr()) if rd is not None else None, slope_out,

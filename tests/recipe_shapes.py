@@ -29,6 +29,7 @@ class Op:
     k: int
     d: int = 1
     u: int = 0                                   # > 0: ConvTranspose1d with stride u
+    pad: int = None                              # explicit padding; None: the recipes' (k - u) // 2 / 'same'
 
     @property
     def transposed(self):
@@ -36,13 +37,16 @@ class Op:
 
     @property
     def padding(self):
+        if self.pad is not None:
+            return self.pad
         return (self.k - self.u) // 2 if self.u else (self.k * self.d - self.d) // 2
 
     @property
     def name(self):
+        p = "" if self.pad is None else f"p{self.pad}"
         if self.u:
-            return f"convT{self.cin}-{self.cout}u{self.u}k{self.k}"
-        return f"conv{self.cin}-{self.cout}k{self.k}d{self.d}"
+            return f"convT{self.cin}-{self.cout}u{self.u}k{self.k}{p}"
+        return f"conv{self.cin}-{self.cout}k{self.k}d{self.d}{p}"
 
     def kwargs(self):
         if self.u:
@@ -69,9 +73,11 @@ class Op:
 
     @property
     def halo(self):
-        if self.u:
+        if self.u > 1:
             return self.KT - 1
-        lo, hi = -self.padding, -self.padding + (self.KT - 1) * self.d
+        # stride 1: conv_build runs a ConvTranspose1d as the Conv1d with flipped taps and padding k - 1 - p
+        pc = self.k - 1 - self.padding if self.u else self.padding
+        lo, hi = -pc, -pc + (self.KT - 1) * self.d
         return max(0, -lo) + max(0, hi)
 
     @property
@@ -92,7 +98,7 @@ class Op:
 
     def form(self, B, T, precision="f16x3"):
         """(kernel id as tests/test_gpu_recipe_shapes.py names it, GEMM rows per launch group, tile width in output columns)"""
-        Tq = T + self.ntaps - 1 if self.u else self.out_len(T)
+        Tq = T + self.ntaps - 1 if self.u > 1 else self.out_len(T)
         if precision == "f32":
             return "conv_mfma_kernel", self.group_rows, None
         WN = 4 // self.WM

@@ -170,8 +170,9 @@ def _kernel_id(line):
     return base
 
 
-def _child(group, precision, out):
-    """run the group's cases in order.  Only a failed assertion moves on to the next case: any other error (a failed launch, a
+def _child(group, precision, out, cases_fn=None):
+    """run the group's cases in order (cases_fn: another table of the same form, tests/test_gpu_conv_geometry.py).
+    Only a failed assertion moves on to the next case: any other error (a failed launch, a
     HIP error) ends the process at once, after recording what was done, so nothing more is started on a device in doubt."""
     sys.path.insert(0, ROOT)
     torch.set_num_threads(16)
@@ -180,7 +181,7 @@ def _child(group, precision, out):
     _lib.set_precision(precision)
     man = os.environ["AMP_LAUNCH_MANIFEST"]
     res = {}
-    for name, fn, _ in group_cases(group, precision):
+    for name, fn, _ in (cases_fn or group_cases)(group, precision):
         n0 = sum(1 for _ in open(man)) if os.path.exists(man) else 0
         err, fatal, ratio = None, None, None
         try:
@@ -201,15 +202,15 @@ def _child(group, precision, out):
 # ------------------------------------------------------------------------------------------------------------------------------
 # parent side: ONE test per (group, precision), so that each child process starts exactly once whatever the number of workers
 # ------------------------------------------------------------------------------------------------------------------------------
-def _run_group(group, precision, tmp_path):
+def _run_group(group, precision, tmp_path, cases_fn=None, script=None, title="recipe shapes"):
     out, man = tmp_path / "results.json", tmp_path / "manifest.tsv"
     env = dict(os.environ, AMP_LAUNCH_MANIFEST=str(man), AMP_PRECISION=precision)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), group, precision, str(out)], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.abspath(script or __file__), group, precision, str(out)], capture_output=True, text=True,
                        env=env, timeout=900)
     res = json.load(open(out)) if out.exists() else {}
     problems, table = [], []
     bound = ACT_BOUND if group == "act1d" else BOUND
-    for name, _, kernels in group_cases(group, precision):
+    for name, _, kernels in (cases_fn or group_cases)(group, precision):
         if name not in res:
             problems.append(f"{name}: not run (the child ended first)")
             continue
@@ -221,7 +222,7 @@ def _run_group(group, precision, tmp_path):
         ratio = c["ratio"]
         table.append(f"{precision:6s} {name:34s} {' + '.join(c['kernels']):34s} "
                      f"{'-' if ratio is None else f'{ratio / bound:.3f}':>7s}  {' | '.join(c['launches'])}")
-    print(f"\n# recipe shapes, group {group}, {precision}: case, kernels, largest error / bound ({bound:g}), launch\n" + "\n".join(table))
+    print(f"\n# {title}, group {group}, {precision}: case, kernels, largest error / bound ({bound:g}), launch\n" + "\n".join(table))
     assert r.returncode == 0 and not problems, f"child exit {r.returncode}\n" + "\n".join(problems) + "\n" + r.stderr[-2000:]
 
 
