@@ -285,7 +285,8 @@ int amp_dwconv(const float* x_dev, const float* w_dev, const float* bias_dev, co
                int dilation, float* y_dev, void* stream);
 /* ConvFlow's spline step (modules/flow/modules.py:435-458 + modules/transformer/transforms.py:56-215): the piecewise
  * rational-quadratic transform with linear tails of one channel of z [B, 2, T] given h [B, 3*num_bins - 1, T] (masked
- * here), both channels * mask; flip_in / flip_out fold the neighbouring Flip layers (:315-321) in.  z_out != z. */
+ * here), both channels * mask; flip_in / flip_out fold the neighbouring Flip layers (:315-321) in.  z_out != z.
+ * PRECONDITION: both masks are 0 / 1 FACTORS: z and h must be finite in the columns t >= lens[b] too. */
 int amp_spline_flow(const float* z_dev, const float* h_dev, const int* lens_dev, int B, int T, int num_bins,
                     int filter_channels, float tail_bound, int inverse, int flip_in, int flip_out, float* z_out_dev,
                     void* stream);
@@ -295,11 +296,14 @@ int amp_spline_flow(const float* z_dev, const float* h_dev, const int* lens_dev,
 int amp_spline_flow_proj(const float* z_dev, const float* hc_dev, const float* proj_w_dev, const float* proj_b_dev, const int* lens_dev,
                          int B, int C, int T, int num_bins, int filter_channels, float tail_bound, int inverse, int flip_in, int flip_out,
                          float* z_out_dev, void* stream);
-/* ElementwiseAffine reverse: (x - m) * exp(-logs) * mask (modules/flow/modules.py:338-340); m, logs [C]. */
+/* ElementwiseAffine reverse: (x - m) * exp(-logs) * mask (modules/flow/modules.py:338-340); m, logs [C].
+ * PRECONDITION: the mask is a 0 / 1 FACTOR: x must be finite in the columns t >= lens[b] too (the duration predictor hands it the
+ * output of a spline step, which is the Gaussian draw times zero there). */
 int amp_affine_reverse(const float* x_dev, const float* m_dev, const float* logs_dev, const int* lens_dev, int B, int C, int T,
                        float* y_dev, void* stream);
 /* emb(tokens) * scale, transposed to [B, hidden, T] and masked (TextEncoder.forward vits.py:58-62); tokens int64 [B, T],
- * weight [n_vocab, hidden]. */
+ * weight [n_vocab, hidden].  Token ids are clamped to [0, n_vocab) in every column, so the columns t >= lens[b] may hold any id;
+ * the mask is a 0 / 1 FACTOR on a (finite) weight. */
 int amp_embed_tokens(const long long* tokens_dev, const float* weight_dev, const int* lens_dev, int B, int T, int hidden,
                      int n_vocab, float scale, float* y_dev, void* stream);
 /* w_ceil = ceil(exp(logw) * mask * length_scale) [B, T], its running sum (int32 [B, T]) and y_len = max(sum, 1)
@@ -451,7 +455,10 @@ int amp_wn_gate(const float* a_dev, const float* cond_dev, long long cond_batch_
                 int T, void* stream);
 /* WN residual/skip update (modules/flow/modules.py:144-151): not last: x = (x + rs[:, :H]) * mask,
  * out += rs[:, H:]; last: out += rs.  first != 0 starts `out` from zero (torch.zeros_like, :127).
- * lens_dev: int32 [B] valid lengths (sequence_mask, utils/util.py:618-622) or NULL for no mask. */
+ * lens_dev: int32 [B] valid lengths (sequence_mask, utils/util.py:618-622) or NULL for no mask.
+ * PRECONDITION: the mask is a 0 / 1 FACTOR here, as in the reference: x and rs must be finite in the columns t >= lens[b] too (WN's
+ * unfused path assigns zero to x beyond the lengths before its first layer and runs its convs densely, so they are); `out` is
+ * not masked at all. */
 int amp_wn_accumulate(float* x_dev, float* out_dev, const float* rs_dev, const int32_t* lens_dev, int B, int H, int T,
                       int first, int last, void* stream);
 /* x[b, :, t >= lens[b]] = 0   (`* x_mask`, vits.py:147,149; modules/flow/modules.py:152,381,383) */
@@ -463,7 +470,9 @@ int amp_coupling_apply(float* x_dev, const float* m_dev, const int32_t* lens_dev
 /* Flip.forward: torch.flip(x, [1]) (modules/flow/modules.py:314-321); y must not alias x. */
 int amp_flip_channels(const float* x_dev, float* y_dev, int B, int C, int T, void* stream);
 /* PosteriorEncoder sampling (models/tts/vits/vits.py:150-151): stats = [m ; logs] [B, 2C, T],
- * z = (m + eps * exp(logs)) * mask. */
+ * z = (m + eps * exp(logs)) * mask.
+ * PRECONDITION: the mask is a 0 / 1 FACTOR: stats and eps must be finite in the columns t >= lens[b] too (PosteriorEncoder assigns
+ * zero to stats there just before, and eps is a full Gaussian draw); z is then zero there. */
 int amp_posterior_sample(const float* stats_dev, const float* eps_dev, const int32_t* lens_dev, float* z_dev, int B,
                          int C, int T, void* stream);
 

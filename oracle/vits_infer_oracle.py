@@ -62,14 +62,15 @@ def relative_self_attention(sd, p, x, x_mask, n_heads, window):
     ar = torch.arange(T)
     off = ar.view(1, T) - ar.view(T, 1) + window                  # [i, j] -> r + window
     near = ((off >= 0) & (off <= 2 * window)).to(x.dtype)
-    off = off.clamp(0, 2 * window)
-    ek = sd[p + ".emb_rel_k"][0][off] * near.unsqueeze(-1)         # [T, T, dk]
-    ev = sd[p + ".emb_rel_v"][0][off] * near.unsqueeze(-1)
-    scores = scores + torch.einsum("bhdi,ijd->bhij", qs, ek)
+    off = off.clamp(0, 2 * window).expand(B, n_heads, T, T)
+    # the band |r| <= window only: [B, H, T, 2w+1] per query instead of a [T, T, dk] table (long utterances)
+    rel = torch.einsum("bhdi,rd->bhir", qs, sd[p + ".emb_rel_k"][0])
+    scores = scores + rel.gather(-1, off) * near
     mask = x_mask.unsqueeze(2) * x_mask.unsqueeze(-1)              # [B, 1, T, T]   (Encoder.forward :65)
     scores = scores.masked_fill(mask == 0, -1e4)
     prob = torch.softmax(scores, dim=-1)
-    out = torch.einsum("bhij,bhdj->bhdi", prob, v) + torch.einsum("bhij,ijd->bhdi", prob, ev)
+    band = torch.zeros_like(rel).scatter_add_(-1, off, prob * near)   # band[i, r] = p[i, i + r - window]
+    out = torch.einsum("bhij,bhdj->bhdi", prob, v) + torch.einsum("bhir,rd->bhdi", band, sd[p + ".emb_rel_v"][0])
     return _conv(sd, p + ".conv_o", out.reshape(B, C, T))
 
 

@@ -70,6 +70,84 @@ def test_rel_attention_falls_back_outside_the_tile_kernel():
     ek, ev = (torch.randn(2 * window + 1, dk, generator=g).cuda() for _ in range(2))
     out = hip_ops.rel_attention(q, k, v, ek, ev, None, H, window)
     assert torch.isfinite(out).all()
+    # ... and it is the reference's attention: against the oracle in fp64 (identity projections: q = k = v), with and without
+    # lengths, at the bound of test_ops_vs_oracle
+    for lens in (None, [13]):
+        ld = torch.tensor(lens, dtype=torch.int32).cuda() if lens is not None else None
+        same = hip_ops.rel_attention(q, q, q, ek, ev, ld, H, window).cpu()
+        assert torch.isfinite(same).all()
+        want, ms = _oracle_attention(q.cpu(), ek.cpu(), ev.cpu(), lens, H, window)
+        assert ((same.double() - want) * ms).abs().max().item() <= 2e-5, lens
+
+
+def _oracle_attention(x, ek, ev, lens, H, window):
+    """vio.relative_self_attention in fp64 with identity projections (q = k = v = x) -> (out, [B, 1, T] mask of the valid queries)"""
+    B, C, T = x.shape
+    sd = {"a.emb_rel_k": ek.double().unsqueeze(0), "a.emb_rel_v": ev.double().unsqueeze(0)}
+    for n in "qkvo":
+        sd[f"a.conv_{n}.weight"], sd[f"a.conv_{n}.bias"] = torch.eye(C, dtype=torch.float64).unsqueeze(-1), torch.zeros(C, dtype=torch.float64)
+    ms = _mask(torch.tensor(lens if lens is not None else [T] * B), T).double()
+    return vio.relative_self_attention(sd, "a", x.double(), ms, H, window), ms
+
+
+# rel_attention_run (vits_text.hip) launches the tiled kernel while its dynamic LDS fits 150 KB, in floats
+#   RA_QB * dk (queries) + RA_QB * 16 + RA_QB (relative scores, row sums) + RA_QB * Tp (the scores of RA_QB queries against ALL keys,
+#   Tp = T rounded up to 4) + 32 * dk (both embeddings) + dk * (RA_KT + 1) (one key / value tile; two when T <= RA_KT and both fit)
+# and the one-query kernel beyond: the term that grows is RA_QB * Tp, so the switch is a length, derived here from the same formula.
+RA_QB, RA_KT, RA_LDS = 16, 128, 150 * 1024
+
+
+def _tiled_lds_bytes(dk, T):
+    Tp = (T + 3) & ~3
+    fixed = (RA_QB * dk + RA_QB * 16 + RA_QB + RA_QB * Tp + 32 * dk) * 4
+    kv = dk * (RA_KT + 1) * 4
+    return fixed + (2 if (T <= RA_KT and fixed + 2 * kv <= RA_LDS) else 1) * kv
+
+
+def _last_tiled_T(dk):
+    T = RA_KT
+    while _tiled_lds_bytes(dk, T + 4) <= RA_LDS:
+        T += 4
+    return T
+
+
+ATTN_DK = 96                                     # config/vits.json: 192 channels, 2 heads
+ATTN_SWITCH = _last_tiled_T(ATTN_DK)
+
+
+@pytest.mark.parametrize("T", [128, 129, 1024, ATTN_SWITCH, ATTN_SWITCH + 4, 2048],
+                         ids=["one_tile", "two_tiles", "1024", "last_tiled", "first_row", "2048"])
+def test_rel_attention_across_the_form_switch(T):
+    """dk = 96, 2 heads, window 4, ragged: one key tile / several; the last length the tiled kernel's LDS holds and the first one
+    that goes to the one-query kernel; a length well beyond.  Each against the oracle in fp64 on the valid queries, and -- where
+    the tiled kernel takes the shape -- tiled == one-query bit for bit."""
+    from amphion_amd import _lib
+    from amphion_amd.modules import hip_ops
+
+    assert RA_KT < ATTN_SWITCH < 2048 and _tiled_lds_bytes(ATTN_DK, ATTN_SWITCH) <= RA_LDS < _tiled_lds_bytes(ATTN_DK, ATTN_SWITCH + 1)
+    H, dk, window = 2, ATTN_DK, 4
+    lens = [T, T - 1, T // 2 + 1]
+    B, C = len(lens), H * dk
+    g = torch.Generator().manual_seed(T)
+    x = torch.randn(B, C, T, generator=g)
+    ek, ev = (torch.randn(2 * window + 1, dk, generator=g) * 0.3 for _ in range(2))
+    ld = torch.tensor(lens, dtype=torch.int32).cuda()
+    xd, ekd, evd = x.cuda(), ek.cuda(), ev.cuda()
+    got = hip_ops.rel_attention(xd, xd, xd, ekd, evd, ld, H, window)
+    want, ms = _oracle_attention(x, ek, ev, lens, H, window)
+    err = ((got.cpu().double() - want) * ms).abs().max().item()
+    print(f"\n[rel_attention] T={T} ({'tiled' if T <= ATTN_SWITCH else 'one-query'} form; the tiled one holds T <= {ATTN_SWITCH}): {err:.3e}")
+    assert torch.isfinite(got.cpu()[ms.bool().expand(B, C, T)]).all() and err <= 2e-5, err
+    L = _lib.lib()
+    try:
+        _lib.check(L.amp_set_rel_attention_tiled(0))
+        row = hip_ops.rel_attention(xd, xd, xd, ekd, evd, ld, H, window)
+    finally:
+        _lib.check(L.amp_set_rel_attention_tiled(1))
+    assert torch.equal(got, row)
+    # the merged-projection form takes the same decision on the same shape
+    qkv = torch.cat([x, x, x], 1).contiguous().cuda()
+    assert torch.equal(hip_ops.rel_attention_qkv(qkv, ekd, evd, ld, H, window), got)
 
 
 @pytest.mark.parametrize("C,T,lens", [(192, 100, [100, 37, 1]), (24, 33, [33, 32, 31]), (300, 70, [64, 70, 5]), (7, 1, [1, 1, 0])])
