@@ -140,6 +140,23 @@ _SIGNATURES = {
     "amp_dw_sample_step": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                    c_size_t, c_void_p]),
     "amp_dw_destroy": (None, [c_void_p]),
+    "amp_fvq_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                               POINTER(c_void_p), POINTER(c_void_p)]),
+    "amp_fvq_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_fvq_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "amp_fvq_check": (c_int, [c_void_p, c_void_p]),
+    "amp_fvq_destroy": (None, [c_void_p]),
+    "amp_codec_unit_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_codec_unit_fused": (c_int, [c_void_p]),
+    "amp_set_codec_unit_fusion": (c_int, [c_int]),
+    "amp_codec_unit_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_codec_unit_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_codec_unit_destroy": (None, [c_void_p]),
+    "amp_sconv_create": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_sconv_out_len": (c_int, [c_void_p, c_int]),
+    "amp_sconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_sconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "amp_sconv_destroy": (None, [c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
@@ -259,6 +276,7 @@ def finalizer(owner, destroy, handle):
     return weakref.finalize(owner, _destroy, destroy, handle.value)
 
 
+AMP_ERR_INVALID = -1
 AMP_ERR_UNSUPPORTED = -4
 AMP_ERR_RANGE = -6
 

@@ -186,6 +186,24 @@ struct DwLayerArgs {
 size_t dw_layer_lds_bytes(int C, int n_mel, bool f32);
 hipError_t launch_dw_layer(DwLayerArgs a, int B, bool f32, hipStream_t stream);
 
+// Arguments of the codec encoder's fused residual unit (codec_unit_f16x3.hip), codec.py:60-76 in one launch
+constexpr int CU_TN = 64;   // output columns per workgroup
+struct CodecUnitArgs {
+    const float* x;            // [B, C, T] input and residual
+    float* y;                  // [B, C, T]; must NOT alias x (other tiles read x's halo)
+    const uint4* wp1;          // [C, 7 C] (tap-major K) as packed A fragments
+    const uint4* wp2;          // [C, C]
+    const float* bias1;        // [C]
+    const float* bias2;        // [C]
+    const float *alpha1, *invb1, *alpha2, *invb2;   // Snake of each conv's input: alpha and 1 / (alpha + 1e-9), [C]
+    int C, T, d;
+    int tiles_per_item;        // set by the launcher
+    float inv1, inv2;          // 1 / (16 * 2^s) of each matrix
+    unsigned* range_flag;      // see ConvArgs
+};
+size_t codec_unit_lds_bytes(int C, int d);
+hipError_t launch_codec_unit(CodecUnitArgs a, int B, hipStream_t stream);
+
 struct ConvPlan {
     int KT;      // taps compiled into the kernel (1,2,3,5,7,11)
     int WM, WN;  // waves along M / N (WM*WN == 4)

@@ -33,10 +33,13 @@ CLASS_TARGETS = {
 
 # Vocos (models/codec/amphion_codec/vocos.py:824-881), the vocoder of Vevo / VevoSing (models/vc/vevo/vevo_utils.py:117-118,
 # models/svc/vevosing/vevosing_utils.py:96) and of the MaskGCT codec decoder (models/codec/amphion_codec/codec.py:372-382).
-# It has its own one-shot finder: _Finder leaves sys.meta_path once the registries and the generator modules are patched,
+# CodecEncoder / CodecDecoder (models/codec/amphion_codec/codec.py:100-428) are what maskgct_utils.build_acoustic_codec constructs
+# (models/tts/maskgct/maskgct_utils.py:66-72): the prompt's wave -> codes and the codes -> latent -> wave path of MaskGCT / DebaTTS / Metis.
+# They have their own one-shot finder: _Finder leaves sys.meta_path once the registries and the generator modules are patched,
 # whether or not a codec package is ever imported.
 CODEC_CLASS_TARGETS = {
     "models.codec.amphion_codec.vocos": ("Vocos",),
+    "models.codec.amphion_codec.codec": ("CodecEncoder", "CodecDecoder"),
 }
 
 
@@ -113,8 +116,8 @@ class _ClassPatchLoader(importlib.abc.Loader):
         _patch_classes(module, module.__name__, CODEC_CLASS_TARGETS)
 
 
-class _CodecFinder(importlib.abc.MetaPathFinder):
-    """One shot per module of CODEC_CLASS_TARGETS; leaves sys.meta_path when all of them are patched."""
+class _OneShotClassFinder(importlib.abc.MetaPathFinder):
+    """One shot per module of its pending set; leaves sys.meta_path when all of them are patched."""
 
     def __init__(self, pending):
         self._pending = set(pending)
@@ -137,16 +140,28 @@ class _CodecFinder(importlib.abc.MetaPathFinder):
         return spec
 
 
+class _CodecFinder(_OneShotClassFinder):
+    """Vocos: gone from sys.meta_path once models.codec.amphion_codec.vocos is patched, whether or not the codec itself is ever imported"""
+
+
+class _CodecModelFinder(_OneShotClassFinder):
+    """CodecEncoder / CodecDecoder (models.codec.amphion_codec.codec)"""
+
+
+_CODEC_FINDERS = {"models.codec.amphion_codec.vocos": _CodecFinder, "models.codec.amphion_codec.codec": _CodecModelFinder}
+
+
 def _install_codec():
-    pending = []
+    pending = {}
     for t in CODEC_CLASS_TARGETS:
         m = sys.modules.get(t)
         if m is None:
-            pending.append(t)
+            pending.setdefault(_CODEC_FINDERS[t], []).append(t)
         elif not getattr(m, "__amphion_amd_patched__", False):
             _patch_classes(m, t, CODEC_CLASS_TARGETS)
-    if pending and not any(isinstance(f, _CodecFinder) for f in sys.meta_path):
-        sys.meta_path.insert(0, _CodecFinder(pending))
+    for cls, targets in pending.items():
+        if not any(type(f) is cls for f in sys.meta_path):
+            sys.meta_path.insert(0, cls(targets))
 
 
 def install(diffwave=None):

@@ -94,7 +94,7 @@ typedef struct amp_gen amp_gen;
  * any n_fft in [64, 4096] (mixed-radix kernels: compile-time butterflies for the primes 2 .. 13, a run-time radix pass for larger prime factors;
  * powers of two keep their kernels); 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision /
  * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024); 144 (additive): the DiffWave entry
- * points amp_dw_*. */
+ * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -636,6 +636,63 @@ int amp_dw_forward(const amp_dw* h, const float* audio_dev, int L, const float* 
 int amp_dw_sample_step(const amp_dw* h, float* audio_dev, int L, float step, float c1, float c2, float sigma, const float* noise_dev,
                        const float* cond_dev, int B, int F, void* ws_dev, size_t ws_bytes, void* stream);
 void amp_dw_destroy(amp_dw* h);
+
+/* ---- Amphion acoustic codec (models/codec/amphion_codec/codec.py, quantize/): what MaskGCT builds as CodecEncoder + CodecDecoder ---- */
+
+/* Residual factorized VQ in eval mode (csrc/fvq.hip; quantize/residual_vq.py:68-152, factorized_vector_quantize.py:52-127), exact fp32.
+ * amp_fvq_create: per level l < num_quantizers the FOLDED in_project [d, D] + bias [d], codebook [K, d], FOLDED out_project [D, d] + bias [D],
+ *   as arrays of num_quantizers host pointers; the four projection arrays are all NULL when input_dim == codebook_dim (nn.Identity).
+ *   Covered: D <= 1024, d <= 32, K <= 16384, N <= 32; anything else AMP_ERR_UNSUPPORTED.
+ * amp_fvq_encode = ResidualVQ.forward: z [B, D, T] -> codes int64 [n_quantizers, B, T] and (zq_dev not NULL) quantized_out [B, D, T], the sum
+ *   of the levels' z_q, and (all_zq_dev not NULL) every level's z_q [n_quantizers, B, D, T] (all_quantized); ONE launch for all levels, the residual stays on chip.  Equal distances resolve to the LOWEST index, as
+ *   (-dist).max(1)[1] does.  The distance keeps the reference's expression and order, (sum e^2 - 2 e.c) + sum c^2 on normalised operands.
+ * amp_fvq_decode = ResidualVQ.vq2emb: codes -> out [B, D, T].  An index outside [0, K) reads row 0 instead (never out of bounds) and sets a
+ *   device flag of the handle; amp_fvq_check synchronises `stream`, returns AMP_ERR_INVALID if that happened since the last check, and clears it
+ *   (the op-level counterpart of amp_range_check).
+ * No allocation and no synchronisation in encode / decode; deterministic; a frame never depends on what it is batched with. */
+typedef struct amp_fvq amp_fvq;
+int amp_fvq_create(int input_dim, int codebook_dim, int codebook_size, int num_quantizers, int use_l2_normalize,
+                   const float* const* in_w_host, const float* const* in_b_host, const float* const* codebook_host,
+                   const float* const* out_w_host, const float* const* out_b_host, amp_fvq** out);
+int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_quantizers, long long* codes_dev, float* zq_dev, float* all_zq_dev,
+                   void* stream);
+int amp_fvq_decode(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, float* out_dev, void* stream);
+int amp_fvq_check(amp_fvq* h, void* stream);
+void amp_fvq_destroy(amp_fvq* h);
+
+/* ResidualUnit of the codec encoder (codec.py:60-76): y = x + conv1x1(snake_2(conv7(snake_1(x)))), Snake1d as codec.py:34-39
+ * (x + (alpha + 1e-9)^-1 sin^2(alpha x)), conv7 = Conv1d(C, C, 7, dilation, padding 3 * dilation).  alpha*_host [C], w1_host [C, C, 7] and
+ * w2_host [C, C, 1] FOLDED, biases [C].  The fused launch (csrc/codec_unit_f16x3.hip) is built for AMP_PRECISION_F16X3 with C % 32 == 0, C <= 192 and
+ * dilation <= 9 and needs no workspace; the default policy uses it up to C = 96, where it is the faster route (amp_codec_unit_fused returns 1;
+ * amp_set_codec_unit_fusion(1) uses it wherever it is built).  Otherwise -- wider units, and every unit under AMP_PRECISION_F32 -- the handle
+ * runs amp_snake -> conv -> amp_snake -> conv (+ residual) on the existing kernels with a workspace of amp_codec_unit_workspace_bytes (two
+ * [B, C, T] tensors).  The f16x3 forms feed the op-level range flag (amp_range_check).
+ * y_dev must not alias x_dev. */
+typedef struct amp_codec_unit amp_codec_unit;
+int amp_codec_unit_create(int channels, int dilation, const float* alpha1_host, const float* w1_host, const float* b1_host, const float* alpha2_host,
+                          const float* w2_host, const float* b2_host, amp_codec_unit** out);
+int amp_codec_unit_fused(const amp_codec_unit* h);
+/* Which route handles created AFTER the call take: -1 (default) the measured policy, 0 the four launches everywhere, 1 the fused launch wherever
+ * it is built -- an A/B switch for tools/codec_bench.py and the tests. */
+int amp_set_codec_unit_fusion(int mode);
+size_t amp_codec_unit_workspace_bytes(const amp_codec_unit* h, int B, int T);
+int amp_codec_unit_forward(const amp_codec_unit* h, const float* x_dev, int B, int T, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream);
+void amp_codec_unit_destroy(amp_codec_unit* h);
+
+/* The strided down-sampling conv of EncoderBlock (codec.py:86-93): Conv1d(cin, cout, k = 2 * stride, stride, padding), optionally preceded by
+ * Snake1d (alpha_dev [cin] on the device, NULL = none).  amp_conv_create keeps refusing strided convs; this entry runs one as a small
+ * kernel that applies the activation and folds stride and padding into the channel axis ([B, cin, T] -> [B, cin * stride, T_out + 1], in
+ * the workspace) followed by a k = 2 stride-1 conv on the implicit-GEMM kernels with the weight re-indexed at create time.
+ * T_out = floor((T + 2 padding - 2 stride) / stride) + 1 (amp_sconv_out_len); T need not be a multiple of the stride.  weight_host
+ * [cout, cin, 2 * stride] FOLDED.  x [B, cin, T] -> y [B, cout, T_out]; ws_dev: amp_sconv_workspace_bytes(h, B, T) bytes.
+ * Grid limit: B * cin * ceil((T_out + 1) * stride / 256) < 2^31, else AMP_ERR_UNSUPPORTED. */
+typedef struct amp_sconv amp_sconv;
+int amp_sconv_create(int cin, int cout, int stride, int padding, const float* weight_host, const float* bias_host, amp_sconv** out);
+int amp_sconv_out_len(const amp_sconv* h, int T);
+size_t amp_sconv_workspace_bytes(const amp_sconv* h, int B, int T);
+int amp_sconv_forward(const amp_sconv* h, const float* x_dev, int B, int T, const float* alpha_dev, void* ws_dev, size_t ws_bytes, float* y_dev,
+                      void* stream);
+void amp_sconv_destroy(amp_sconv* h);
 
 #ifdef __cplusplus
 }
