@@ -1,5 +1,6 @@
 // Host-only declarations shared by the host units of libamphion_hip.so (runtime.hip, conv_host.hip, generator.hip, ops_abi.hip,
-// and the host halves of pw_f16x3.hip and diffwave.hip).  Kernel argument structs and launch_* prototypes stay in amp_internal.h.
+// fvq.hip, codec.hip, diffwave.hip and the host half of pw_f16x3.hip).  Kernel argument structs and launch_* prototypes stay in
+// amp_internal.h.
 #pragma once
 #include <math.h>
 
@@ -43,6 +44,24 @@ namespace amp {
 
 // hipMalloc + hipMemcpy of `bytes` host bytes; on success the caller owns *out (hipFree), on failure nothing is left allocated
 int device_upload(const void* host, size_t bytes, void** out);
+
+// Every device allocation of a handle: upload() is device_upload() into memory the owner frees with the handle.
+struct DeviceAllocs {
+    std::vector<void*> owned;
+    DeviceAllocs() = default;
+    DeviceAllocs(const DeviceAllocs&) = delete;
+    DeviceAllocs& operator=(const DeviceAllocs&) = delete;
+    ~DeviceAllocs() {
+        for (void* p : owned) (void)hipFree(p);
+    }
+    int upload(const void* host, size_t bytes, void** out) {
+        if (int rc = device_upload(host, bytes, out); rc != AMP_OK) return rc;
+        owned.push_back(*out);
+        return AMP_OK;
+    }
+    template <class T, class P>
+    int upload(const std::vector<T>& v, P** out) { return upload(v.data(), v.size() * sizeof(T), (void**)out); }
+};
 
 // Process-wide default for handles created from now on: AMP_PRECISION=f32|f16x3, amp_set_precision() (runtime.hip)
 int default_precision();
@@ -130,6 +149,24 @@ std::vector<_Float16> pack_a_f16x3(int row_blocks, int k16, int taps, size_t pad
                         wp[((ent + 1) * 64 + lane) * 8 + e] = lo;
                     }
     return wp;
+}
+
+// One fp32 matrix W(m, i), m < rows, i < cols -> the A fragments of row_blocks x k16 (zero outside the matrix) after the per-matrix 2^s:
+// the packed operand of pw_f16x3.hip, dw_layer_f16x3.hip and codec_unit_f16x3.hip.  *inv_scale = 1 / (16 * 2^s) undoes it and the x16
+// of the staged activations.  Refuses a non-finite weight in `who`'s name.  (conv_build has taps and pad entries: its own pack_a_f16x3.)
+template <class View>
+int pack_matrix_f16x3(const char* who, int rows, int cols, int row_blocks, int k16, View W, std::vector<_Float16>* wp, float* inv_scale) {
+    float wmax = 0.f;
+    for (int m = 0; m < rows; ++m)
+        for (int i = 0; i < cols; ++i) {
+            const float w = fabsf(W(m, i));
+            if (!(w < 1e30f)) { set_error("%s: non-finite weight", who); return AMP_ERR_INVALID; }
+            wmax = fmaxf(wmax, w);
+        }
+    const float wscale = pow2_weight_scale(wmax);
+    *inv_scale = 1.f / (16.f * wscale);
+    *wp = pack_a_f16x3(row_blocks, k16, 1, 0, wscale, [&](int m, int i, int) { return (m < rows && i < cols) ? W(m, i) : 0.f; });
+    return AMP_OK;
 }
 
 // ---- convs and the fused forms built from them (conv_host.hip) ------------------------------------------------------

@@ -312,6 +312,14 @@ inline hipError_t ensure_dynamic_lds(size_t bytes) {
     return hipSuccess;
 }
 
+// set the LDS attribute, launch 256-thread workgroups on a 1-D grid, hand back the launch status
+template <auto Kernel, class Args>
+inline hipError_t launch_dynamic_lds(unsigned grid, size_t lds, hipStream_t stream, const Args& a) {
+    if (hipError_t e = ensure_dynamic_lds<Kernel>(lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(256), lds, stream, a);
+    return hipGetLastError();
+}
+
 // Which kernels a stretch of launch_* calls issued, as rocprofv3 prints them ("pair_strip_kernel<11, 2, 2, 4, 320, 2, 4, 1>"):
 // while the calling thread points tl_kernel_log at a string (a profiled amp_gen_forward does, per resblock), every launch
 // appends its kernel's name once (" | "-joined) -- bench.py reports the variant the policy actually picked, not a literal.

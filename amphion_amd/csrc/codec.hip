@@ -50,10 +50,7 @@ struct amp_codec_unit {
     float *b1 = nullptr, *b2 = nullptr, *al1 = nullptr, *ib1 = nullptr, *al2 = nullptr, *ib2 = nullptr;
     float inv1 = 1.f, inv2 = 1.f;
     std::unique_ptr<amp_conv> c1, c2;     // the unfused route
-    std::vector<void*> owned;
-    ~amp_codec_unit() {
-        for (void* p : owned) (void)hipFree(p);
-    }
+    DeviceAllocs dev;
 };
 
 struct amp_sconv {
@@ -61,19 +58,10 @@ struct amp_sconv {
     std::unique_ptr<amp_conv> conv;       // Conv1d(cin * s, cout, k = 2, padding 0)
 };
 
-static int cu_upload(amp_codec_unit* h, const void* host, size_t bytes, void** out) {
-    AMP_RC(device_upload(host, bytes, out));
-    h->owned.push_back(*out);
-    return AMP_OK;
-}
-
-static std::vector<_Float16> cu_pack(const float* W, int rows, int K, float* inv_scale, int taps, int C) {
-    float wmax = 0.f;
-    for (size_t i = 0; i < (size_t)rows * K; ++i) wmax = fmaxf(wmax, fabsf(W[i]));
-    const float wscale = pow2_weight_scale(wmax);
-    *inv_scale = 1.f / (16.f * wscale);
-    // GEMM column i = tap * C + c of the [rows, C, taps] conv weight
-    return pack_a_f16x3(rows / 32, K / 16, 1, 0, wscale, [&](int m, int i, int) { const int tap = i / C, c = i - tap * C; return W[((size_t)m * C + c) * taps + tap]; });
+// the [C, C, taps] conv weight as the [C, taps * C] GEMM matrix: column i = tap * C + c
+static int cu_pack(const float* W, int C, int taps, std::vector<_Float16>* wp, float* inv_scale) {
+    return pack_matrix_f16x3("amp_codec_unit_create", C, taps * C, C / 32, taps * C / 16,
+                             [&](int m, int i) { const int tap = i / C, c = i - tap * C; return W[((size_t)m * C + c) * taps + tap]; }, wp, inv_scale);
 }
 
 static long long sconv_out_len(const amp_sconv* h, long long T) {
@@ -93,23 +81,27 @@ int amp_codec_unit_create(int channels, int dilation, const float* alpha1_host, 
     h->C = C; h->d = d; h->precision = default_precision();
     const bool built = h->precision == PREC_F16X3 && C % 32 == 0 && C <= 192 && d <= 9;
     h->fused = built && g_unit_fusion != 0 && (g_unit_fusion == 1 || C <= kUnitFusedPolicyMaxC);
-    for (size_t i = 0; i < (size_t)C * C * 7; ++i)
-        if (!(fabsf(w1_host[i]) < 1e30f)) { set_error("amp_codec_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
-    for (size_t i = 0; i < (size_t)C * C; ++i)
-        if (!(fabsf(w2_host[i]) < 1e30f)) { set_error("amp_codec_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
-    AMP_RC(cu_upload(h.get(), alpha1_host, sizeof(float) * C, (void**)&h->al1));
-    AMP_RC(cu_upload(h.get(), alpha2_host, sizeof(float) * C, (void**)&h->al2));
+    // the fused route's packer refuses non-finite weights itself; the four-launch route (both precisions) has this check only
+    if (!h->fused) {
+        for (size_t i = 0; i < (size_t)C * C * 7; ++i)
+            if (!(fabsf(w1_host[i]) < 1e30f)) { set_error("amp_codec_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
+        for (size_t i = 0; i < (size_t)C * C; ++i)
+            if (!(fabsf(w2_host[i]) < 1e30f)) { set_error("amp_codec_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
+    }
+    AMP_RC(h->dev.upload(alpha1_host, sizeof(float) * C, (void**)&h->al1));
+    AMP_RC(h->dev.upload(alpha2_host, sizeof(float) * C, (void**)&h->al2));
     if (h->fused) {
         std::vector<float> ib1(C), ib2(C);
         for (int c = 0; c < C; ++c) { ib1[c] = 1.0f / (alpha1_host[c] + 0.000000001f); ib2[c] = 1.0f / (alpha2_host[c] + 0.000000001f); }
-        AMP_RC(cu_upload(h.get(), ib1.data(), sizeof(float) * C, (void**)&h->ib1));
-        AMP_RC(cu_upload(h.get(), ib2.data(), sizeof(float) * C, (void**)&h->ib2));
-        AMP_RC(cu_upload(h.get(), b1_host, sizeof(float) * C, (void**)&h->b1));
-        AMP_RC(cu_upload(h.get(), b2_host, sizeof(float) * C, (void**)&h->b2));
-        const std::vector<_Float16> p1 = cu_pack(w1_host, C, 7 * C, &h->inv1, 7, C);
-        const std::vector<_Float16> p2 = cu_pack(w2_host, C, C, &h->inv2, 1, C);
-        AMP_RC(cu_upload(h.get(), p1.data(), p1.size() * sizeof(_Float16), (void**)&h->wp1));
-        AMP_RC(cu_upload(h.get(), p2.data(), p2.size() * sizeof(_Float16), (void**)&h->wp2));
+        AMP_RC(h->dev.upload(ib1, &h->ib1));
+        AMP_RC(h->dev.upload(ib2, &h->ib2));
+        AMP_RC(h->dev.upload(b1_host, sizeof(float) * C, (void**)&h->b1));
+        AMP_RC(h->dev.upload(b2_host, sizeof(float) * C, (void**)&h->b2));
+        std::vector<_Float16> p1, p2;
+        AMP_RC(cu_pack(w1_host, C, 7, &p1, &h->inv1));
+        AMP_RC(cu_pack(w2_host, C, 1, &p2, &h->inv2));
+        AMP_RC(h->dev.upload(p1, &h->wp1));
+        AMP_RC(h->dev.upload(p2, &h->wp2));
     } else {
         h->c1 = std::make_unique<amp_conv>();
         h->c1->cin = C; h->c1->cout = C; h->c1->k = 7; h->c1->dilation = d; h->c1->padding = 3 * d;

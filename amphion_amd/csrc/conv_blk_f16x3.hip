@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
         if (fast) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float bv = a.bias ? a.bias[mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] : 0.f;
+                const float bv = a.bias ? a.bias[acc_row(r, hi, mb * 32)] : 0.f;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) acc[mi][t][r] = bv;
             }
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
                 const float* rp = a.res + wave_base;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float* rr_ = rp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                    const float* rr_ = rp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                     for (int t = 0; t < NI; ++t) acc[mi][t][r] += rr_[lane_off + 32 * t];
                 }
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
                 const float* yp = a.y + wave_base;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                    const float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                     for (int t = 0; t < NI; ++t) acc[mi][t][r] += yr_[lane_off + 32 * t];
                 }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
         } else if (!a.res && a.mode == 0) {   // transposed convs / ragged last tiles without residual: bias only
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int m = acc_row(r, hi, mb * 32);
                 const int o = (up == 1) ? m : m / up;
                 const float bv = a.bias ? a.bias[o] : 0.f;
 #pragma unroll
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int m = acc_row(r, hi, mb * 32);
                 const int o = (up == 1) ? m : m / up;
                 const int rr = m - o * up;
                 const float bv = a.bias ? a.bias[o] : 0.f;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
                 stage4_f16((tok && (ch0 + 0) < a.Cin) ? xs[cc][it][0] : 0.f, (tok && (ch0 + 1) < a.Cin) ? xs[cc][it][1] : 0.f,
                            (tok && (ch0 + 2) < a.Cin) ? xs[cc][it][2] : 0.f, (tok && (ch0 + 3) < a.Cin) ? xs[cc][it][3] : 0.f,
                            kpos, kneg, range_max, fh.u, fl.u);
-                const int o2 = (((qd >> 1) * S + col) << 1) + (qd & 1);
+                const int o2 = bplane_idx(qd, col, S);
                 dst[o2] = fh.u;
                 dst[4 * S + o2] = fl.u;
             }
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
             float* yp = a.y + ((size_t)item * a.Cout + (size_t)mb * 32) * a.Tout;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) {
                     float v = acc[mi][t][r] * a.inv_scale;
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void conv_blk_kernel(const ConvArgs a) {
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int m = acc_row(r, hi, mb * 32);
                 const int o = (up == 1) ? m : m / up;
                 const int rr = m - o * up;
                 const size_t rowoff = ((size_t)item * a.Cout + o) * a.Tout;

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
     if (fast) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rowc = (r & 3) + 8 * (r >> 2);
+            const int rowc = acc_row(r);
             const float bv = a.bias ? a.bias[mb * 32 + rowc + 4 * hi] : 0.f;
 #pragma unroll
             for (int t = 0; t < NI; ++t) acc[t][r] = bv;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
             const float* rp = a.res + wave_base;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float* rr_ = rp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                const float* rr_ = rp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) acc[t][r] += rr_[lane_off + 32 * t];
             }
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
             const float* yp = a.y + wave_base;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                const float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) acc[t][r] += yr_[lane_off + 32 * t];
             }
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
     } else if (!a.res && a.mode == 0) {   // transposed convs / ragged tiles without residual: bias only
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int m = acc_row(r, hi, mb * 32);
             const int o = (up == 1) ? m : m / up;
             const float bv = (m < a.M && a.bias) ? a.bias[o] : 0.f;
 #pragma unroll
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
     } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int row = acc_row(r, hi);
             const int m = mb * 32 + row;
             const bool mok = m < a.M;
             const int o = (up == 1) ? m : m / up;
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
             stage4_f16((tok && (ch0 + 0) < a.Cin) ? xs[it][0] : 0.f, (tok && (ch0 + 1) < a.Cin) ? xs[it][1] : 0.f, (tok && (ch0 + 2) < a.Cin) ? xs[it][2] : 0.f, (tok && (ch0 + 3) < a.Cin) ? xs[it][3] : 0.f,
                        kpos, kneg, range_max, fh.u, fl.u);
             // uint2 index inside a plane: ((octet * S + col) * 2 + half)
-            const int o2 = (((qd >> 1) * S + col) << 1) + (qd & 1);
+            const int o2 = bplane_idx(qd, col, S);
             dst[o2] = fh.u;
             dst[4 * S + o2] = fl.u;
         }
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
         float* yp = a.y + wave_base;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+            float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
             for (int t = 0; t < NI; ++t) {
                 float v = acc[t][r] * a.inv_scale;
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x3_kernel(const ConvArgs a) {
     } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int row = acc_row(r, hi);
             const int m = mb * 32 + row;
             if (m < a.M) {
                 const int o = (up == 1) ? m : m / up;

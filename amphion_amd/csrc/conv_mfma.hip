@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
     if (fast) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rowc = (r & 3) + 8 * (r >> 2);
+            const int rowc = acc_row(r);
             const float bv = a.bias ? a.bias[mb * 32 + rowc + 4 * hi] : 0.f;
 #pragma unroll
             for (int t = 0; t < NI; ++t) acc[t][r] = bv;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
             const float* rp = a.res + wave_base;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float* rr_ = rp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                const float* rr_ = rp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) acc[t][r] += rr_[lane_off + 32 * t];
             }
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
             const float* yp = a.y + wave_base;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+                const float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
                 for (int t = 0; t < NI; ++t) acc[t][r] += yr_[lane_off + 32 * t];
             }
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
     } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int row = acc_row(r, hi);
             const int m = mb * 32 + row;
             const bool mok = m < a.M;
             const int o = (up == 1) ? m : m / up;
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
         float* yp = a.y + wave_base;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float* yr_ = yp + (size_t)((r & 3) + 8 * (r >> 2)) * a.Tout;
+            float* yr_ = yp + (size_t)acc_row(r) * a.Tout;
 #pragma unroll
             for (int t = 0; t < NI; ++t) {
                 float v = acc[t][r];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
     } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int row = acc_row(r, hi);
             const int m = mb * 32 + row;
             if (m < a.M) {
                 const int o = (up == 1) ? m : m / up;

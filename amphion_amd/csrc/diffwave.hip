@@ -158,28 +158,15 @@ struct amp_dw {
     std::map<std::string, size_t> expected;          // key -> element count
     std::map<std::string, std::vector<float>> w;     // host copies until finalize()
     std::vector<DwLayer> layers;
-    std::vector<void*> owned;                        // every device allocation of the handle
+    DeviceAllocs dev;                                // every device allocation of the handle
     float *table = nullptr, *p1w = nullptr, *p1b = nullptr, *p2w = nullptr, *p2b = nullptr, *wd = nullptr, *bd = nullptr;
     float *up_w[2] = {nullptr, nullptr}, *up_b[2] = {nullptr, nullptr};
     float *in_w = nullptr, *in_b = nullptr, *sk_w = nullptr, *sk_b = nullptr, *out_w = nullptr, *out_b = nullptr;
-    ~amp_dw() {
-        for (void* p : owned) (void)hipFree(p);
-    }
 };
 
-static int dw_upload(amp_dw* h, const void* host, size_t bytes, void** out) {
-    AMP_RC(device_upload(host, bytes, out));
-    h->owned.push_back(*out);
-    return AMP_OK;
-}
-
-// [rows, cols] fp32 (rows a multiple of 32) -> f16x3 A fragments after a per-matrix 2^s (amp_host.h: pack_a_f16x3)
-static std::vector<_Float16> dw_pack(const std::vector<float>& W, int rows, int cols, float* inv_scale) {
-    float wmax = 0.f;
-    for (float v : W) wmax = fmaxf(wmax, fabsf(v));
-    const float wscale = pow2_weight_scale(wmax);
-    *inv_scale = 1.f / (16.f * wscale);
-    return pack_a_f16x3(rows / 32, (cols + 15) / 16, 1, 0, wscale, [&](int m, int i, int) { return i < cols ? W[(size_t)m * cols + i] : 0.f; });
+// [rows, cols] fp32 (rows a multiple of 32) -> f16x3 A fragments after a per-matrix 2^s
+static int dw_pack(const std::vector<float>& W, int rows, int cols, std::vector<_Float16>* wp, float* inv_scale) {
+    return pack_matrix_f16x3("amp_dw_finalize", rows, cols, rows / 32, (cols + 15) / 16, [&](int m, int i) { return W[(size_t)m * cols + i]; }, wp, inv_scale);
 }
 
 static bool dw_overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -369,10 +356,7 @@ int amp_dw_finalize(amp_dw* h) {
     for (const auto& kv : h->expected)
         if (!h->w.count(kv.first)) { set_error("amp_dw_finalize: missing weight '%s'", kv.first.c_str()); return AMP_ERR_MISSING_WEIGHT; }
     const int C = h->d.residual_channels, N = h->d.residual_layers, M = h->d.n_mel, K = 3 * C + M;
-    auto up = [&](const std::string& key, float** dst) {
-        const std::vector<float>& v = h->w[key];
-        return dw_upload(h, v.data(), v.size() * sizeof(float), (void**)dst);
-    };
+    auto up = [&](const std::string& key, float** dst) { return h->dev.upload(h->w[key], dst); };
 #define DW_UP(key, dst) if (int rc = up(key, dst); rc != AMP_OK) return rc
     DW_UP("input_projection.weight", &h->in_w);
     DW_UP("input_projection.bias", &h->in_b);
@@ -408,19 +392,21 @@ int amp_dw_finalize(amp_dw* h) {
         std::vector<float> b1(h->w[p + "dilated_conv.bias"]);
         const std::vector<float>& bc = h->w[p + "conditioner_projection.bias"];
         for (int m = 0; m < 2 * C; ++m) b1[m] += bc[m];
-        if (int rc = dw_upload(h, b1.data(), b1.size() * sizeof(float), (void**)&ly.b1); rc != AMP_OK) return rc;
-        if (int rc = up(p + "output_projection.bias", &ly.b2); rc != AMP_OK) return rc;
+        AMP_RC(h->dev.upload(b1, &ly.b1));
+        AMP_RC(up(p + "output_projection.bias", &ly.b2));
         // both arithmetics are uploaded: amp_dw_set_precision switches a finalized handle (the sampler's exact-fp32 repeat)
-        if (int rc = dw_upload(h, W1.data(), W1.size() * sizeof(float), (void**)&ly.w1f); rc != AMP_OK) return rc;
-        if (int rc = dw_upload(h, W2.data(), W2.size() * sizeof(float), (void**)&ly.w2f); rc != AMP_OK) return rc;
-        const std::vector<_Float16> p1 = dw_pack(W1, 2 * C, K, &ly.inv1), p2 = dw_pack(W2, 2 * C, C, &ly.inv2);
-        if (int rc = dw_upload(h, p1.data(), p1.size() * sizeof(_Float16), (void**)&ly.wp1); rc != AMP_OK) return rc;
-        if (int rc = dw_upload(h, p2.data(), p2.size() * sizeof(_Float16), (void**)&ly.wp2); rc != AMP_OK) return rc;
+        AMP_RC(h->dev.upload(W1, &ly.w1f));
+        AMP_RC(h->dev.upload(W2, &ly.w2f));
+        std::vector<_Float16> p1, p2;
+        AMP_RC(dw_pack(W1, 2 * C, K, &p1, &ly.inv1));
+        AMP_RC(dw_pack(W2, 2 * C, C, &p2, &ly.inv2));
+        AMP_RC(h->dev.upload(p1, &ly.wp1));
+        AMP_RC(h->dev.upload(p2, &ly.wp2));
         std::copy(h->w[p + "diffusion_projection.weight"].begin(), h->w[p + "diffusion_projection.weight"].end(), wd.begin() + (size_t)i * C * 512);
         std::copy(h->w[p + "diffusion_projection.bias"].begin(), h->w[p + "diffusion_projection.bias"].end(), bd.begin() + (size_t)i * C);
     }
-    if (int rc = dw_upload(h, wd.data(), wd.size() * sizeof(float), (void**)&h->wd); rc != AMP_OK) return rc;
-    if (int rc = dw_upload(h, bd.data(), bd.size() * sizeof(float), (void**)&h->bd); rc != AMP_OK) return rc;
+    AMP_RC(h->dev.upload(wd, &h->wd));
+    AMP_RC(h->dev.upload(bd, &h->bd));
     h->w.clear();
     h->finalized = true;
     return AMP_OK;

@@ -4,20 +4,17 @@
 //     z    = sigmoid(a[:C]) * tanh(a[C:])                    (first half gate, second half filter)
 //     r    = output_projection(z)                            (C -> 2C, k = 1)
 //     x_out = (x + r[:C]) / sqrt(2),   skip_out = skip_in + r[C:]
-// as two GEMMs around a seam.  GEMM 1 has K = 3C + n_mel: the three taps are three SEPARATELY staged column tiles of x at t - d, t, t + d
-// (the dilation never enters a halo: d = 512 costs what d = 1 costs), the conditioner rows follow as further K.  The gated product goes
-// x16 / split into LDS and is the B operand of GEMM 2.  One workgroup owns 64 output columns of one item and all 2C rows: no atomics
-// (except the range flag), fixed summation order, a batch row never depends on what it is batched with.
-//
-// f16x3 arithmetic as pw_f16x3.hip: weights pre-split on the host after a per-matrix 2^s, activations x16 and split while staged, hh + hl + lh
-// MFMA terms into f32.  The whole K extent of a tile is staged at once ([plane][channel octet][column][8 x f16], one ds_read_b128 per B
-// fragment); the seam re-uses the front of the same LDS after a barrier, which keeps two workgroups per CU at the recipe width.
-// Waves are 2 x 2: wave (wm, wn) owns columns 32 wn .. 32 wn + 31; in GEMM 1 the gate row block p AND its filter row block p + C / 32 for
-// p = wm, wm + 2, .. (so sigmoid * tanh is formed in registers); in GEMM 2 the row blocks wm, wm + 2, .. of the 2C output rows.
+// as the two GEMMs around a seam of wholek_f16x3.h (layouts, wave grid, arithmetic: there).  GEMM 1 has K = 3C + n_mel: the three taps are
+// three SEPARATELY staged column tiles of x at t - d, t, t + d (the dilation never enters a halo: d = 512 costs what d = 1 costs), the
+// conditioner rows follow as further K.  The gated product is the B operand of GEMM 2; re-using the front of the same LDS keeps two
+// workgroups per CU at the recipe width.  One workgroup owns 64 output columns of one item and all 2C rows: no atomics (except the
+// range flag), fixed summation order, a batch row never depends on what it is batched with.  In GEMM 1 a wave contracts the gate row
+// block p AND its filter row block p + C / 32 for p = wm, wm + 2, .. (so sigmoid * tanh is formed in registers); in GEMM 2 the row blocks
+// wm, wm + 2, .. of the 2C output rows.
 //
 // dw_layer_f32_kernel is the exact-fp32 form of the same layer (AMP_PRECISION_F32, and the repeat after a range report): the same
 // per-tap staging, fp32 in LDS, one fmaf chain per output on the vector ALU.  It is not meant to be fast.
-#include "f16x3_device.h"
+#include "wholek_f16x3.h"
 
 namespace amp {
 
@@ -78,12 +75,10 @@ __global__ __launch_bounds__(256, 2) void dw_layer_f16x3_kernel(const DwLayerArg
             }
             uint2 fh, fl;
             stage4_f16(v[0], v[1], v[2], v[3], 16.f, 16.f, range_max, fh, fl);
-            const int o2 = (((qd >> 1) * TN + lane) << 1) + (qd & 1);
-            dst[o2] = fh;
-            dst[2 * PLANE + o2] = fl;
+            bplane_store(dst, 2 * PLANE, bplane_idx(qd, lane, TN), fh, fl);
         }
     }
-    if (a.range_flag && __any(range_max > 65504.f) && lane == 0) atomicOr(a.range_flag, 1u);
+    raise_range(a.range_flag, range_max, lane);
     __syncthreads();
 
     // ---- GEMM 1 + gate: z = sigmoid(gate) * tanh(filter), kept in registers until every wave has left the staged operand ----
@@ -93,84 +88,42 @@ __global__ __launch_bounds__(256, 2) void dw_layer_f16x3_kernel(const DwLayerArg
     for (int pi = 0; pi < NPW; ++pi) {
         const int p = wm + 2 * pi;
         if (p >= NP) break;
-        f32x16 ag, af;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ag[r] = af[r] = 0.f;
-        const uint4* wg = a.wp1 + (size_t)p * K16 * 128 + lane;
-        const uint4* wf = a.wp1 + (size_t)(NP + p) * K16 * 128 + lane;
-        Frag gh, gl, fh, fl;
-        gh.u = wg[0]; gl.u = wg[64]; fh.u = wf[0]; fl.u = wf[64];
-        for (int k = 0; k < K16; ++k) {
-            Frag ngh, ngl, nfh, nfl;
-            const int kn = k + 1 < K16 ? k + 1 : k;
-            ngh.u = wg[kn * 128]; ngl.u = wg[kn * 128 + 64]; nfh.u = wf[kn * 128]; nfl.u = wf[kn * 128 + 64];
-            Frag bh, bl;
-            bh.u = dw_smem[2 * k * TN + rd0];
-            bl.u = dw_smem[PLANE + 2 * k * TN + rd0];
-            ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh.h, bh.h, ag, 0, 0, 0);
-            af = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh.h, bh.h, af, 0, 0, 0);
-            ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(gh.h, bl.h, ag, 0, 0, 0);
-            af = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh.h, bl.h, af, 0, 0, 0);
-            ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(gl.h, bh.h, ag, 0, 0, 0);
-            af = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl.h, bh.h, af, 0, 0, 0);
-            gh = ngh; gl = ngl; fh = nfh; fl = nfl;
-        }
+        f32x16 acc[2][1];                  // gate, filter
+        acc_zero(acc[0][0]);
+        acc_zero(acc[1][0]);
+        const APack A{a.wp1 + (size_t)p * K16 * 128 + lane, (size_t)NP * K16 * 128, K16};
+        Frag ah[2], al[2];
+        afrag_load<2>(ah, al, A.wa, A.mbs);
+        gemm_wholek<2, true>(acc, ah, al, A, 0, K16, dw_smem, PLANE, TN, rd0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = p * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float g = ag[r] * a.inv1 + a.bias1[m];
-            const float f = af[r] * a.inv1 + a.bias1[C + m];
+            const int m = acc_row(r, hi, p * 32);
+            const float g = acc[0][0][r] * a.inv1 + a.bias1[m];
+            const float f = acc[1][0][r] * a.inv1 + a.bias1[C + m];
             z[pi][r] = (1.f / (1.f + expf(-g))) * tanhf(f);
         }
     }
     __syncthreads();
 
-    // ---- seam: registers 4j .. 4j + 3 of a lane are channels 32 p + 8 j + 4 hi + 0 .. 3 of column 32 wn + l31 ----
+    // ---- seam: |z| <= 1, no range report ----
     const int PLANE2 = (C >> 3) * TN;
-    {
-        uint2* dst = reinterpret_cast<uint2*>(dw_smem);
-#pragma unroll
-        for (int pi = 0; pi < NPW; ++pi) {
-            const int p = wm + 2 * pi;
-            if (p >= NP) break;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const amp_f32x2 v01 = {z[pi][4 * j] * 16.f, z[pi][4 * j + 1] * 16.f};
-                const amp_f32x2 v23 = {z[pi][4 * j + 2] * 16.f, z[pi][4 * j + 3] * 16.f};
-                uint2 sh, sl;
-                split4_f16(v01, v23, sh, sl);
-                const int o2 = (((p * 4 + j) * TN + wn * 32 + l31) << 1) + hi;
-                dst[o2] = sh;
-                dst[2 * PLANE2 + o2] = sl;
-            }
-        }
-    }
+    seam_store<NPW>(z, reinterpret_cast<uint2*>(dw_smem), 2 * PLANE2, TN, wm, wn * 32 + l31, hi, NP, nullptr);
     __syncthreads();
 
     // ---- GEMM 2 + epilogue: rows [0, C) the residual, rows [C, 2C) the skip ----
     const int KC = C >> 4;
     const float sqrt2 = 1.41421356237309504880f;
     for (int rb = wm; rb < 2 * NP; rb += 2) {
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const uint4* w2 = a.wp2 + (size_t)rb * KC * 128 + lane;
-        for (int k = 0; k < KC; ++k) {
-            Frag wh, wl, bh, bl;
-            wh.u = w2[k * 128];
-            wl.u = w2[k * 128 + 64];
-            bh.u = dw_smem[2 * k * TN + rd0];
-            bl.u = dw_smem[PLANE2 + 2 * k * TN + rd0];
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh.h, bh.h, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh.h, bl.h, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl.h, bh.h, acc, 0, 0, 0);
-        }
+        f32x16 acc[1][1];
+        acc_zero(acc[0][0]);
+        Frag ah, al;
+        gemm_wholek<1, false>(acc, &ah, &al, APack{a.wp2 + (size_t)rb * KC * 128 + lane, 0, KC}, 0, KC, dw_smem, PLANE2, TN, rd0);
         const int q = q0 + wn * 32 + l31;
         if (q >= L) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float v = acc[r] * a.inv2 + a.bias2[m];
+            const int m = acc_row(r, hi, rb * 32);
+            const float v = acc[0][0][r] * a.inv2 + a.bias2[m];
             if (rb < NP) {
                 const size_t o = ((size_t)item * C + m) * L + q;
                 a.x_out[o] = (a.x[o] + v) / sqrt2;
@@ -270,14 +223,8 @@ hipError_t launch_dw_layer(DwLayerArgs a, int B, bool f32, hipStream_t stream) {
     const int npw = (a.C + 63) / 64;
     note_kernel("dw_layer_f16x3_kernel", npw);
     note_work(grid, gf, mb, "diffwave layer C=%d n_mel=%d d=%d L=%d B=%d", a.C, a.n_mel, a.d, a.L, B);
-    if (npw == 1) {
-        if (hipError_t e = ensure_dynamic_lds<&dw_layer_f16x3_kernel<1>>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(dw_layer_f16x3_kernel<1>, dim3(grid), dim3(256), lds, stream, a);
-    } else {
-        if (hipError_t e = ensure_dynamic_lds<&dw_layer_f16x3_kernel<2>>(lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(dw_layer_f16x3_kernel<2>, dim3(grid), dim3(256), lds, stream, a);
-    }
-    return hipGetLastError();
+    return npw == 1 ? launch_dynamic_lds<&dw_layer_f16x3_kernel<1>>(grid, lds, stream, a)
+                    : launch_dynamic_lds<&dw_layer_f16x3_kernel<2>>(grid, lds, stream, a);
 }
 
 }  // namespace amp

@@ -1,5 +1,6 @@
 // Device building blocks shared by the split-f16 ("f16x3") MFMA kernels (conv_f16x3.hip, conv_blk_f16x3.hip, conv_small_f16x3_body.h,
-// pair_f16x3_body.h, pair_strip_f16x3.hip, rb_f16x3.hip, ampb_f16x3.hip, pw_f16x3.hip; conv_mfma.hip takes the tile order).
+// pair_f16x3_body.h, pair_strip_f16x3.hip, rb_f16x3.hip, ampb_f16x3.hip; pw_f16x3.hip, dw_layer_f16x3.hip and codec_unit_f16x3.hip through
+// wholek_f16x3.h, which adds the blocks of the whole-K two-GEMM family; conv_mfma.hip takes the tile order and the accumulator row map).
 // Every fused form is bit-identical to the launches it replaces because all of them split an operand, form a product term and walk
 // the tiles through the SAME text: the one below.  Device code only; host declarations and argument structs are in amp_internal.h.
 #pragma once
@@ -36,16 +37,42 @@ __device__ __forceinline__ int tile_order(unsigned bid, int nbx, bool ragged, in
     return bx;
 }
 
-// One tap of the split product over N column tiles: Whi*Xhi, Whi*Xlo, Wlo*Xhi -- three sweeps in THIS order (the
-// arithmetic contract every kernel form keeps; the dropped Wlo*Xlo term is 2^-22 relative).
+// ---- three layout facts every kernel of the family relies on --------------------------------------------------------------------
+// v_mfma_f32_32x32x16_f16: register r of lane (hi = lane >> 5, l31 = lane & 31) of an accumulator tile holds column l31 of row
+// acc_row(r, hi) of the 32-row block; acc_row(r) is the part without the lane term, for the sites that fold 4 * hi into a pointer.
+// `base` (the block's first row) is summed first, left to right: hipcc's address arithmetic follows the association of this sum.
+__device__ __forceinline__ int acc_row(int r, int hi = 0, int base = 0) { return base + (r & 3) + 8 * (r >> 2) + 4 * hi; }
+// A staged B operand is [plane hi | lo][channel octet][column][8 x f16]: one ds_read_b128 per fragment.  Staging writes channel QUADS
+// (uint2): the index of quad qd at column col inside a plane S columns wide.
+__device__ __forceinline__ int bplane_idx(int qd, int col, int S) { return (((qd >> 1) * S + col) << 1) + (qd & 1); }
+// range_max is the running maximum of |staged operand| (stage4_f16 / seam4_f16); beyond the f16 range the split form does not hold
+// the value: one lane of the wave reports it (amp_host.h: RangeGuard).
+__device__ __forceinline__ void raise_range(unsigned* flag, float range_max, int lane) {
+    if (flag && __any(range_max > 65504.f) && lane == 0) atomicOr(flag, 1u);
+}
+
+// The split product of MI row blocks x NI column tiles over one k-extent: Whi*Xhi, Whi*Xlo, Wlo*Xhi -- three sweeps over ALL tiles in
+// THIS order (the arithmetic contract every kernel form keeps; the dropped Wlo*Xlo term is 2^-22 relative).  The only
+// text of the family that issues the MFMA.
+template <int MI, int NI>
+__device__ __forceinline__ void mfma3_tiles(f32x16 (*acc)[NI], const Frag* a_h, const Frag* a_l, const Frag* bh, const Frag* bl) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[i].h, bh[t].h, acc[i][t], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[i].h, bl[t].h, acc[i][t], 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[i].h, bh[t].h, acc[i][t], 0, 0, 0);
+}
+// the same for one row block over N column tiles (one conv tap): the form the conv family uses
 template <int N>
 __device__ __forceinline__ void mfma3(f32x16* acc, const Frag& a_h, const Frag& a_l, const Frag* bh, const Frag* bl) {
-#pragma unroll
-    for (int t = 0; t < N; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h.h, bh[t].h, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < N; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h.h, bl[t].h, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < N; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l.h, bh[t].h, acc[t], 0, 0, 0);
+    mfma3_tiles<1, N>(reinterpret_cast<f32x16(*)[N]>(acc), &a_h, &a_l, bh, bl);
 }
 
 // v = hi + lo with hi = f16(v), lo = f16(v - hi): the split-f16 operand form of the f16x3 kernels.

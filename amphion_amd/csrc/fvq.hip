@@ -257,19 +257,8 @@ struct amp_fvq {
     bool proj = false;
     float *w_in = nullptr, *b_in = nullptr, *cb = nullptr, *cbn = nullptr, *cn2 = nullptr, *w_out = nullptr, *b_out = nullptr;
     unsigned* flag = nullptr;
-    std::vector<void*> owned;
-    ~amp_fvq() {
-        for (void* p : owned) (void)hipFree(p);
-    }
+    DeviceAllocs dev;
 };
-
-static int fvq_upload(amp_fvq* h, const std::vector<float>& v, float** out) {
-    void* p = nullptr;
-    AMP_RC(device_upload(v.data(), v.size() * sizeof(float), &p));
-    h->owned.push_back(p);
-    *out = (float*)p;
-    return AMP_OK;
-}
 
 static size_t fvq_lds_bytes(int D, int DP) { return ((size_t)2 * D * FVQ_TF + 2 * DP * FVQ_TF + FVQ_TF * 10) * sizeof(float); }
 
@@ -331,19 +320,17 @@ int amp_fvq_create(int input_dim, int codebook_dim, int codebook_size, int num_q
             memcpy(&bo[(size_t)l * D], out_b_host[l], sizeof(float) * D);
         }
     }
-    AMP_RC(fvq_upload(h.get(), cb, &h->cb));
-    AMP_RC(fvq_upload(h.get(), cbn, &h->cbn));
-    AMP_RC(fvq_upload(h.get(), cn2, &h->cn2));
+    AMP_RC(h->dev.upload(cb, &h->cb));
+    AMP_RC(h->dev.upload(cbn, &h->cbn));
+    AMP_RC(h->dev.upload(cn2, &h->cn2));
     if (proj) {
-        AMP_RC(fvq_upload(h.get(), wi, &h->w_in));
-        AMP_RC(fvq_upload(h.get(), bi, &h->b_in));
-        AMP_RC(fvq_upload(h.get(), wo, &h->w_out));
-        AMP_RC(fvq_upload(h.get(), bo, &h->b_out));
+        AMP_RC(h->dev.upload(wi, &h->w_in));
+        AMP_RC(h->dev.upload(bi, &h->b_in));
+        AMP_RC(h->dev.upload(wo, &h->w_out));
+        AMP_RC(h->dev.upload(bo, &h->b_out));
     }
     const std::vector<float> zero(1, 0.f);
-    float* fl = nullptr;
-    AMP_RC(fvq_upload(h.get(), zero, &fl));
-    h->flag = reinterpret_cast<unsigned*>(fl);
+    AMP_RC(h->dev.upload(zero, &h->flag));
     *out = h.release();
     return AMP_OK;
 }

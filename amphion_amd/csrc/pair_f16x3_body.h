@@ -115,7 +115,7 @@ __device__ __forceinline__ void pair_f16x3_body(const PairArgs& a, const int bid
             struct { uint2 u; } fh, fl;
             stage4_f16(tok ? xs[it][0] : 0.f, tok ? xs[it][1] : 0.f, tok ? xs[it][2] : 0.f, tok ? xs[it][3] : 0.f,
                        kpos, kneg, range_max, fh.u, fl.u);
-            const int o2 = (((qd >> 1) * SX + col) << 1) + (qd & 1);
+            const int o2 = bplane_idx(qd, col, SX);
             dst[o2] = fh.u;
             dst[4 * SX + o2] = fl.u;
         }

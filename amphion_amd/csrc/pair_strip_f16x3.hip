@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
             struct { uint2 u; } fh, fl;
             stage4_f16(tok ? xs[it][0] : 0.f, tok ? xs[it][1] : 0.f, tok ? xs[it][2] : 0.f, tok ? xs[it][3] : 0.f,
                        kpos, kneg, range_max, fh.u, fl.u);
-            const int o2 = (((qd >> 1) * SX + col) << 1) + (qd & 1);
+            const int o2 = bplane_idx(qd, col, SX);
             dst[o2] = fh.u;
             dst[4 * SX + o2] = fl.u;
         }

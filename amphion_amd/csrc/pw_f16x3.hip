@@ -6,9 +6,8 @@
 //     AMP_PW_BIAS_GELU   y = gelu_erf(Wx + b)                 (nn.GELU(), exact erf form)
 //     AMP_PW_SCALE_RES   y = res + gamma (.) (Wx + b)         (layer scale + residual; y may alias res)
 //
-// Arithmetic: the f16x3 scheme of conv_f16x3.hip -- weights pre-split on the host into hi / lo f16 planes after a per-matrix
-// 2^s scale, activations scaled x16 and split while staged, three v_mfma_f32_32x32x16_f16 per product term (Whi Xhi + Whi Xlo +
-// Wlo Xhi) into f32 accumulators, the scale undone in the epilogue, the range flag raised when a staged operand leaves the f16 range.
+// Arithmetic: the f16x3 scheme (f16x3_device.h; operand layouts and fragment loads: wholek_f16x3.h) -- weights pre-split on the host after a
+// per-matrix 2^s, activations x16 and split while staged, the scale undone in the epilogue, the range flag raised by the staging.
 //
 // Tiling.  The contraction is K = Cin (384 .. 4096), there is no halo: a K step stages 64 channels (4 MFMA k-extents), one barrier per
 // step.  Four waves as 2 x 2, each wave MI x NI 32 x 32 accumulator tiles: the 128 x 128 tile (MI = NI = 2: 64 accumulator VGPRs,
@@ -24,7 +23,7 @@
 #include <memory>
 
 #include "amp_host.h"
-#include "f16x3_device.h"
+#include "wholek_f16x3.h"
 #include "gelu_erf.h"
 
 namespace amp {
@@ -109,9 +108,7 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
             uint2 fh, fl;
             stage4_f16((tok && ch0 + 0 < Cin) ? xs[it][0] : 0.f, (tok && ch0 + 1 < Cin) ? xs[it][1] : 0.f,
                        (tok && ch0 + 2 < Cin) ? xs[it][2] : 0.f, (tok && ch0 + 3 < Cin) ? xs[it][3] : 0.f, 16.f, 16.f, range_max, fh, fl);
-            const int o2 = (((qd >> 1) * TN + col) << 1) + (qd & 1);   // uint2 index inside a plane
-            dst[o2] = fh;
-            dst[2 * PLANE + o2] = fl;
+            bplane_store(dst, 2 * PLANE, bplane_idx(qd, col, TN), fh, fl);
         }
     };
 
@@ -121,11 +118,7 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
     Frag ah[PW_KS][MI], al[PW_KS][MI];
 #pragma unroll
     for (int h = 0; h < PW_KS; ++h)
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            ah[h][i].u = wa[i * mbs + h * 128];
-            al[h][i].u = wa[i * mbs + h * 128 + 64];
-        }
+        afrag_load<MI>(ah[h], al[h], wa + h * 128, mbs);
     stage_load(0);
     AMP_PIN_VMEM();
     stage_store(0, 0);
@@ -144,28 +137,10 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
             const uint4* bg = base + (2 * h) * TN;
             Frag bh[NI], bl[NI];
 #pragma unroll
-            for (int t = 0; t < NI; ++t) {
-                bh[t].u = bg[32 * t];
-                bl[t].u = bg[PLANE + 32 * t];
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[h][i].h, bh[t].h, acc[i][t], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[h][i].h, bl[t].h, acc[i][t], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int t = 0; t < NI; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[h][i].h, bh[t].h, acc[i][t], 0, 0, 0);
+            for (int t = 0; t < NI; ++t) bfrag_load(bg, PLANE, 32 * t, bh[t], bl[t]);
+            mfma3_tiles<MI, NI>(acc, ah[h], al[h], bh, bl);
             if (more) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    ah[h][i].u = wa[i * mbs + h * 128];
-                    al[h][i].u = wa[i * mbs + h * 128 + 64];
-                }
+                afrag_load<MI>(ah[h], al[h], wa + h * 128, mbs);
                 AMP_PIN_VMEM();
             }
         }
@@ -176,15 +151,15 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
     for (int s = 0; s + 1 < nsteps; ++s) step(s, true);
     step(nsteps - 1, false);
 
-    if (a.range_flag && __any(range_max > 65504.f) && lane == 0) atomicOr(a.range_flag, 1u);
+    raise_range(a.range_flag, range_max, lane);
 
-    // ---- epilogue: lane (hi, l31), register r of tile (i, t) holds row (r & 3) + 8 (r >> 2) + 4 hi, column 32 t + l31 ----
+    // ---- epilogue: lane (hi, l31), register r of tile (i, t) holds row acc_row(r, hi), column 32 t + l31 ----
     const size_t ybase = (size_t)item * a.Cout * T;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = (mb0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int m = acc_row(r, hi, (mb0 + i) * 32);
             if (m >= a.Cout) continue;
             const float bv = a.bias[m];
             const float gv = EPI == AMP_PW_SCALE_RES ? a.gamma[m] : 0.f;
@@ -281,17 +256,11 @@ int amp_pw_create(int cin, int cout, const float* weight_host, const float* bias
         p->conv->cin = cin; p->conv->cout = cout; p->conv->k = 1;
         AMP_RC(conv_build(p->conv, weight_host, bias.data()));
     } else {
-        float wmax = 0.f;
-        const size_t nw = (size_t)cin * cout;
-        for (size_t i = 0; i < nw; ++i) wmax = fmaxf(wmax, fabsf(weight_host[i]));
-        if (!(wmax < 1e30f)) { set_error("amp_pw_create: non-finite weight"); return AMP_ERR_INVALID; }
-        const float wscale = pow2_weight_scale(wmax);
-        p->inv_scale = 1.f / (16.f * wscale);
         p->nsteps = (cin + PW_KC - 1) / PW_KC;
         const int nmb = (cout + PW_MROWS - 1) / PW_MROWS * (PW_MROWS / 32);
-        const std::vector<_Float16> wp = pack_a_f16x3(nmb, p->nsteps * PW_KS, 1, 0, wscale, [&](int m, int i, int) {
-            return (m < cout && i < cin) ? weight_host[(size_t)m * cin + i] : 0.f;
-        });
+        std::vector<_Float16> wp;
+        AMP_RC(pack_matrix_f16x3("amp_pw_create", cout, cin, nmb, p->nsteps * PW_KS, [&](int m, int i) { return weight_host[(size_t)m * cin + i]; },
+                                 &wp, &p->inv_scale));
         AMP_RC(device_upload(wp.data(), wp.size() * sizeof(_Float16), (void**)&p->wp_dev));
         AMP_RC(device_upload(bias.data(), (size_t)cout * sizeof(float), (void**)&p->bias_dev));
     }
