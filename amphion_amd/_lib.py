@@ -157,6 +157,13 @@ _SIGNATURES = {
     "amp_sconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "amp_sconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "amp_sconv_destroy": (None, [c_void_p]),
+    "amp_tconv_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_tconv_out_len": (c_int, [c_void_p, c_int]),
+    "amp_tconv_fused": (c_int, [c_void_p]),
+    "amp_set_tconv_fusion": (c_int, [c_int]),
+    "amp_tconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_tconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "amp_tconv_destroy": (None, [c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),

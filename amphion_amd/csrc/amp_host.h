@@ -28,6 +28,7 @@ struct amp_conv {
     int nchunks = 0;
     int precision = amp::PREC_F32;  // arithmetic of the contraction, fixed at build time
     int pad_reflect = 0, tanh_out = 0;  // amp_conv_set_option
+    int out_pad = 0;           // ConvTranspose1d output_padding (< stride, <= padding: no new taps, T_out only); set by amp_tconv_create alone
     int gated_H = 0;           // > 0: rows packed for the gate epilogue of conv_small_f16x3.hip (amp_conv_create_gated)
     int Mpad = 0;              // rows of the packed weight
     float wscale = 1.f;        // f16x3: power of two applied to the packed weights
@@ -152,7 +153,7 @@ std::vector<_Float16> pack_a_f16x3(int row_blocks, int k16, int taps, size_t pad
 }
 
 // One fp32 matrix W(m, i), m < rows, i < cols -> the A fragments of row_blocks x k16 (zero outside the matrix) after the per-matrix 2^s:
-// the packed operand of pw_f16x3.hip, dw_layer_f16x3.hip and codec_unit_f16x3.hip.  *inv_scale = 1 / (16 * 2^s) undoes it and the x16
+// the packed operand of pw_f16x3.hip, dw_layer_f16x3.hip, codec_unit_f16x3.hip and tconv_f16x3.hip.  *inv_scale = 1 / (16 * 2^s) undoes it and the x16
 // of the staged activations.  Refuses a non-finite weight in `who`'s name.  (conv_build has taps and pad entries: its own pack_a_f16x3.)
 template <class View>
 int pack_matrix_f16x3(const char* who, int rows, int cols, int row_blocks, int k16, View W, std::vector<_Float16>* wp, float* inv_scale) {

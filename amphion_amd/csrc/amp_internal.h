@@ -204,6 +204,25 @@ struct CodecUnitArgs {
 size_t codec_unit_lds_bytes(int C, int d);
 hipError_t launch_codec_unit(CodecUnitArgs a, int B, hipStream_t stream);
 
+// Arguments of the fused Snake -> ConvTranspose1d(k = 2 s, stride s) kernel (tconv_f16x3.hip): the decoder blocks' up-sampling step in one launch
+constexpr int TC_TN = 64;   // GEMM columns q (input positions) per workgroup
+struct TconvArgs {
+    const float* x;            // [B, cin, T]
+    float* y;                  // [B, cout, Tout]
+    const uint4* wp;           // [cout * s rows (o, r), 2 cin] (tap-major K: w[c, o, r], then w[c, o, r + s]) as packed A fragments
+    const float* bias;         // [cout]
+    const float* alpha;        // [cin] Snake of the input, or nullptr (no activation)
+    int cin, cout, s, p;
+    int T, Tout;
+    int M, NRB;                // GEMM rows cout * s and their 32-row blocks
+    int q_first;               // first column that owns an output sample: p / s
+    int tiles_per_item;        // set by the launcher
+    float inv;                 // 1 / (16 * 2^s) of the matrix
+    unsigned* range_flag;      // see ConvArgs
+};
+size_t tconv_lds_bytes(int cin);
+hipError_t launch_tconv(TconvArgs a, int B, hipStream_t stream);
+
 struct ConvPlan {
     int KT;      // taps compiled into the kernel (1,2,3,5,7,11)
     int WM, WN;  // waves along M / N (WM*WN == 4)

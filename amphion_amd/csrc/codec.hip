@@ -1,6 +1,8 @@
 // Host side of the Amphion codec encoder's building blocks (models/codec/amphion_codec/codec.py:60-143): the residual-unit handle
 // (amp_codec_unit_*: the fused kernel of codec_unit_f16x3.hip where it is built, else the four launches it replaces) and the strided
-// down-sampling conv (amp_sconv_*: Snake + space-to-depth in one small kernel, then a k = 2 conv on the implicit-GEMM kernels).
+// down-sampling conv (amp_sconv_*: Snake + space-to-depth in one small kernel, then a k = 2 conv on the implicit-GEMM kernels); and of the
+// decoder blocks' up-sampling step (amp_tconv_*: Snake + ConvTranspose1d(k = 2 s, stride s) as the fused kernel of tconv_f16x3.hip where it is
+// built, else amp_snake -> the polyphase transposed conv).
 #include <memory>
 
 #include "act1d_math.h"
@@ -52,6 +54,23 @@ struct amp_codec_unit {
     std::unique_ptr<amp_conv> c1, c2;     // the unfused route
     DeviceAllocs dev;
 };
+
+// amp_set_tconv_fusion: -1 the policy, 0 never (snake, then the transposed conv), 1 wherever the fused kernel is built.  Read at create time.
+static int g_tconv_fusion = -1;
+// widest input the policy hands to the fused kernel
+constexpr int kTconvFusedPolicyMaxCin = 384;
+
+struct amp_tconv {
+    int cin = 0, cout = 0, s = 1, p = 0, op = 0, precision = PREC_F16X3;
+    bool fused = false;
+    uint4* wp = nullptr;
+    float* bias = nullptr;
+    float inv = 1.f;
+    std::unique_ptr<amp_conv> conv;       // the two-launch route: ConvTranspose1d(cin, cout, 2 s, s, p) with out_pad = op
+    DeviceAllocs dev;
+};
+
+static long long tconv_out_len(const amp_tconv* h, long long T) { return (T - 1) * h->s - 2ll * h->p + 2ll * h->s + h->op; }
 
 struct amp_sconv {
     int cin = 0, cout = 0, s = 1, p = 0;
@@ -208,5 +227,95 @@ int amp_sconv_forward(const amp_sconv* h, const float* x_dev, int B, int T, cons
 }
 
 void amp_sconv_destroy(amp_sconv* h) { delete h; }
+
+int amp_tconv_create(int cin, int cout, int stride, int padding, int output_padding, const float* weight_host, const float* bias_host, amp_tconv** out) {
+    if (!weight_host || !out) { set_error("amp_tconv_create: null argument"); return AMP_ERR_INVALID; }
+    if (amp_device_count() <= 0) { set_error("amp_tconv_create: no HIP device visible (the HIP path has no CPU fallback)"); return AMP_ERR_HIP; }
+    if (cin < 1 || cout < 1 || stride < 1 || padding < 0 || output_padding < 0) {
+        set_error("amp_tconv_create: cin=%d cout=%d stride=%d padding=%d output_padding=%d", cin, cout, stride, padding, output_padding);
+        return AMP_ERR_INVALID;
+    }
+    if (output_padding >= stride) { set_error("amp_tconv_create: output_padding %d must be smaller than the stride %d", output_padding, stride); return AMP_ERR_INVALID; }
+    // the q = T column is the last one either route walks: its samples reach t = T s + s - 1 - p, and T_out - 1 = T s + s - 1 - 2 p + op
+    if (output_padding > padding) { set_error("amp_tconv_create: output_padding %d > padding %d", output_padding, padding); return AMP_ERR_UNSUPPORTED; }
+    if ((long long)cout * stride > (1 << 24)) { set_error("amp_tconv_create: cout * stride = %lld rows", (long long)cout * stride); return AMP_ERR_UNSUPPORTED; }
+    auto h = std::make_unique<amp_tconv>();
+    h->cin = cin; h->cout = cout; h->s = stride; h->p = padding; h->op = output_padding; h->precision = default_precision();
+    const int s = stride, k = 2 * s;
+    const bool built = h->precision == PREC_F16X3 && cin % 32 == 0 && cin <= 384 && s >= 2 && s <= 8;
+    h->fused = built && g_tconv_fusion != 0 && (g_tconv_fusion == 1 || cin <= kTconvFusedPolicyMaxCin);
+    if (h->fused) {
+        const int M = cout * s;
+        std::vector<_Float16> wp;
+        AMP_RC(pack_matrix_f16x3("amp_tconv_create", M, 2 * cin, (M + 31) / 32, 2 * cin / 16,
+                                 [&](int m, int i) { const int tap = i / cin, c = i - tap * cin, o = m / s, r = m - o * s;
+                                                     return weight_host[((size_t)c * cout + o) * k + r + tap * s]; }, &wp, &h->inv));
+        AMP_RC(h->dev.upload(wp, &h->wp));
+        std::vector<float> b(cout, 0.f);
+        if (bias_host) b.assign(bias_host, bias_host + cout);
+        AMP_RC(h->dev.upload(b, &h->bias));
+    } else {
+        h->conv = std::make_unique<amp_conv>();
+        h->conv->transposed = 1; h->conv->cin = cin; h->conv->cout = cout; h->conv->k = k; h->conv->stride = s; h->conv->padding = padding;
+        h->conv->out_pad = output_padding;
+        AMP_RC(conv_build(h->conv.get(), weight_host, bias_host));
+    }
+    *out = h.release();
+    return AMP_OK;
+}
+
+int amp_set_tconv_fusion(int mode) {
+    if (mode < -1 || mode > 1) { set_error("amp_set_tconv_fusion: mode %d (-1 policy, 0 off, 1 wherever built)", mode); return AMP_ERR_INVALID; }
+    g_tconv_fusion = mode;
+    return AMP_OK;
+}
+
+int amp_tconv_fused(const amp_tconv* h) { return h ? (h->fused ? 1 : 0) : -1; }
+
+int amp_tconv_out_len(const amp_tconv* h, int T) {
+    if (!h) return 0;
+    const long long n = tconv_out_len(h, T);
+    return n < 0 ? 0 : (n > 0x7fffffffll ? 0x7fffffff : (int)n);
+}
+
+size_t amp_tconv_workspace_bytes(const amp_tconv* h, int B, int T) {
+    if (!h || h->fused || B <= 0 || T <= 0) return 0;
+    return (size_t)B * h->cin * T * sizeof(float);
+}
+
+int amp_tconv_forward(const amp_tconv* h, const float* x_dev, int B, int T, const float* alpha_dev, void* ws_dev, size_t ws_bytes, float* y_dev,
+                      void* stream_) {
+    if (!h || !x_dev || !y_dev) { set_error("amp_tconv_forward: null argument"); return AMP_ERR_INVALID; }
+    if (B <= 0 || T <= 0) { set_error("amp_tconv_forward: B=%d T=%d", B, T); return AMP_ERR_INVALID; }
+    const long long Tout = tconv_out_len(h, T);
+    if (Tout <= 0) { set_error("amp_tconv_forward: input too short (T=%d gives T_out=%lld)", T, Tout); return AMP_ERR_INVALID; }
+    if (Tout > (1ll << 30)) { set_error("amp_tconv_forward: T_out=%lld is beyond the kernels' index arithmetic", Tout); return AMP_ERR_UNSUPPORTED; }
+    hipStream_t st = (hipStream_t)stream_;
+    if (h->fused) {
+        const long long nq = (Tout - 1 + h->p) / h->s - h->p / h->s + 1;
+        if ((long long)B * ((nq + TC_TN - 1) / TC_TN) > 0x7fffffffll) {
+            set_error("amp_tconv_forward: B=%d x T=%d is beyond the grid", B, T);
+            return AMP_ERR_UNSUPPORTED;
+        }
+        TconvArgs a{};
+        a.x = x_dev; a.y = y_dev; a.wp = h->wp; a.bias = h->bias; a.alpha = alpha_dev;
+        a.cin = h->cin; a.cout = h->cout; a.s = h->s; a.p = h->p; a.T = T; a.Tout = (int)Tout;
+        a.M = h->cout * h->s; a.NRB = (a.M + 31) / 32; a.q_first = h->p / h->s; a.inv = h->inv;
+        a.range_flag = range_flag_for_current_device();
+        AMP_HIP(launch_tconv(a, B, st));
+        return AMP_OK;
+    }
+    const float* in = x_dev;
+    if (alpha_dev) {
+        const size_t need = amp_tconv_workspace_bytes(h, B, T);
+        if (!ws_dev || ws_bytes < need) { set_error("amp_tconv_forward: workspace %zu < %zu bytes", ws_bytes, need); return AMP_ERR_INVALID; }
+        AMP_HIP(launch_snake(x_dev, (float*)ws_dev, B, h->cin, T, alpha_dev, nullptr, 0, st));
+        in = (const float*)ws_dev;
+    }
+    AMP_RC(conv_run(h->conv.get(), in, B, T, 1.f, nullptr, 1.f, y_dev, 0, 1.f, st));
+    return AMP_OK;
+}
+
+void amp_tconv_destroy(amp_tconv* h) { delete h; }
 
 }  // extern "C"

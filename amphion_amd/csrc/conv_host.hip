@@ -271,7 +271,7 @@ static size_t conv_weight_bytes(const amp_conv* c) { return (size_t)c->Mpad * c-
 
 static int conv_out_len(const amp_conv* c, int T) {
     if (!c->transposed) return T + 2 * c->padding - c->dilation * (c->k - 1);
-    return (T - 1) * c->stride - 2 * c->padding + c->k;
+    return (T - 1) * c->stride - 2 * c->padding + c->k + c->out_pad;
 }
 
 // conv_small_f16x3.hip covers: Conv1d (no polyphase rows), zero padding, 128-row workgroups, k in {1, 3, 5, 7, 11},

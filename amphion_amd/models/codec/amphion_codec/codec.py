@@ -7,6 +7,8 @@
                                                                  else amp_snake -> conv -> amp_snake -> conv + residual (amp_codec_unit_forward)
                                      Snake -> strided conv       Snake + space-to-depth, then a k = 2 conv (amp_sconv_forward)
                    Snake -> last conv (k = 3) [-> tanh]          amp_snake, HipConv1d (tanh on store)
+    DecoderBlock   Snake -> ConvTranspose1d(k = 2 s, stride s)   ONE fused launch (csrc/tconv_f16x3.hip; built to cin = 384, s = 2 .. 8), else amp_snake ->
+                                                                 the polyphase transposed conv (amp_tconv_forward); then 3 x ResidualUnit as above
     CodecDecoder   quantizer (ResidualVQ, "fvq")                 exact-fp32 quantizer kernels (csrc/fvq.hip): quantize / vq2emb one launch each
                    model (use_vocos=True)                        the Vocos of this package
 
@@ -155,6 +157,86 @@ class _StridedConv(ConvParams):
         return out
 
 
+class _TransposedConv(ConvParams):
+    """WNConvTranspose1d(cin, cout, 2 * stride, stride, padding, output_padding) under the reference's keys (weight-norm over dim 0 = the INPUT
+    channels: ``weight_g`` [cin, 1, 1], ``weight_v`` [cin, cout, 2 * stride]); ``forward(x, alpha)`` = conv_transpose(snake(x))
+    (``amp_tconv_forward``)"""
+
+    def __init__(self, cin, cout, stride, padding, output_padding=0):
+        super().__init__(cin, cout, 2 * stride, transposed=True, stride=stride, padding=padding)
+        self.output_padding = output_padding
+        self._h, self._hsig, self._fin = None, None, None
+
+    def _handle(self, device):
+        sig = _sig([p for p in self._parameters.values() if p is not None], device)
+        if self._h is not None and sig == self._hsig:
+            return self._h
+        if self._fin is not None:
+            self._fin()
+        w, b = _host(self.folded_weight()), _host(self.bias)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().amp_tconv_create(self.cin, self.cout, self.stride, self.padding, self.output_padding, _p(w), _p(b), ctypes.byref(h)))
+        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_tconv_destroy", h)
+        return h
+
+    def fused(self, device):
+        return bool(_lib.lib().amp_tconv_fused(self._handle(device)))
+
+    def out_len(self, T):
+        return (T - 1) * self.stride - 2 * self.padding + 2 * self.stride + self.output_padding
+
+    def forward(self, x, alpha=None):
+        x = _check_input(x, self.cin, "transposed conv")
+        B, _, T = x.shape
+        dev = x.device
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            h = self._handle(dev)
+            Tout = L.amp_tconv_out_len(h, T)
+            if Tout < 1:
+                raise ValueError(f"transposed conv: {T} input samples give no output (k = {self.k}, stride {self.stride}, padding {self.padding})")
+            need = L.amp_tconv_workspace_bytes(h, B, T)
+            ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+            out = torch.empty((B, self.cout, Tout), dtype=torch.float32, device=dev)
+            a = None if alpha is None else alpha.detach().reshape(-1).contiguous()
+            _lib.check(L.amp_tconv_forward(h, _p(x), B, T, _p(a), _p(ws), need, _p(out), _lib.current_stream_ptr(dev)))
+        return out
+
+
+def _check_channels(x, channels, who):
+    """the shape first (a host tensor of the wrong width is a ValueError), then the device"""
+    if isinstance(x, torch.Tensor) and (x.dim() != 3 or x.shape[1] != channels):
+        raise ValueError(f"{who}: expected a [B, {channels}, T] input, got {tuple(x.shape)}")
+    return _check_input(x, channels, who)
+
+
+class DecoderBlock(nn.Module):
+    """codec.py:146-165: Snake1d -> WNConvTranspose1d(k = 2 s, stride s, padding s // 2 + s % 2, output_padding s % 2) -> 3 x ResidualUnit.
+    ``output_padding=0`` is DualCodec's form of the same block (model_codec/dac_model.py:119-137)."""
+
+    def __init__(self, input_dim: int = 16, output_dim: int = 8, stride: int = 1, output_padding=None):
+        super().__init__()
+        op = stride % 2 if output_padding is None else output_padding
+        self.input_dim = input_dim
+        self.block = nn.Sequential(Snake1d(input_dim), _TransposedConv(input_dim, output_dim, stride, stride // 2 + stride % 2, op),
+                                   ResidualUnit(output_dim, dilation=1), ResidualUnit(output_dim, dilation=3), ResidualUnit(output_dim, dilation=9))
+
+    def run(self, x):
+        x = self.block[1](x, self.block[0].alpha)
+        for unit in list(self.block)[2:]:
+            x = unit.run(x)
+        return x
+
+    def forward(self, x):
+        x = _check_channels(x, self.input_dim, "DecoderBlock")
+        _check_tensors(self, x.device, "DecoderBlock")
+        with _lib.on_device(x.device):
+            y = self.run(x)
+        _lib.range_check(x.device)
+        return y
+
+
 class EncoderBlock(nn.Module):
     def __init__(self, dim: int = 16, stride: int = 1):
         super().__init__()
@@ -244,7 +326,7 @@ class CodecDecoder(nn.Module):
             raise ValueError(f"Unknown quantizer type {quantizer_type}")
         if not use_vocos:
             raise NotImplementedError("CodecDecoder with use_vocos=False (the convolutional decoder) is not on the HIP path: no shipped config "
-                                      "uses it, and its ConvTranspose1d needs output_padding")
+                                      "uses it")
         self.quantizer = ResidualVQ(input_dim=in_channels, num_quantizers=num_quantizers, codebook_size=codebook_size, codebook_dim=codebook_dim,
                                     quantizer_type=quantizer_type, quantizer_dropout=quantizer_dropout, commitment=commitment,
                                     codebook_loss_weight=codebook_loss_weight, use_l2_normlize=use_l2_normlize)

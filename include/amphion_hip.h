@@ -94,7 +94,8 @@ typedef struct amp_gen amp_gen;
  * any n_fft in [64, 4096] (mixed-radix kernels: compile-time butterflies for the primes 2 .. 13, a run-time radix pass for larger prime factors;
  * powers of two keep their kernels); 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision /
  * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024); 144 (additive): the DiffWave entry
- * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*. */
+ * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*;
+ * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -693,6 +694,32 @@ size_t amp_sconv_workspace_bytes(const amp_sconv* h, int B, int T);
 int amp_sconv_forward(const amp_sconv* h, const float* x_dev, int B, int T, const float* alpha_dev, void* ws_dev, size_t ws_bytes, float* y_dev,
                       void* stream);
 void amp_sconv_destroy(amp_sconv* h);
+
+/* The up-sampling step of the DAC-style decoder blocks (codec.py:146-165; DualCodec model_codec/dac_model.py:129-146):
+ * ConvTranspose1d(cin, cout, k = 2 * stride, stride, padding, output_padding), optionally preceded by Snake1d (alpha_dev [cin] on the device,
+ * NULL = none).  weight_host [cin, cout, 2 * stride] FOLDED (the weight-norm of a ConvTranspose1d is over dim 0 = cin), bias_host [cout] or NULL.
+ * x [B, cin, T] -> y [B, cout, T_out], T_out = (T - 1) * stride - 2 * padding + 2 * stride + output_padding (amp_tconv_out_len).
+ * output_padding < stride (else AMP_ERR_INVALID) and output_padding <= padding (else AMP_ERR_UNSUPPORTED: it lengthens T_out only, the column
+ * of input position T is the last either route computes); the reference's blocks have padding ceil(stride / 2), output_padding stride % 2.
+ * The fused launch (csrc/tconv_f16x3.hip: activation, both polyphase taps and the scatter in one kernel, no workspace) is built for
+ * AMP_PRECISION_F16X3 with cin % 32 == 0, cin <= 384 and 2 <= stride <= 8, any cout; the default policy uses it wherever it is built
+ * (amp_tconv_fused returns 1; the A/B measurement that could narrow this is in DESIGN.md 12).  Otherwise -- wider inputs, other strides, and every handle under AMP_PRECISION_F32 -- the
+ * handle runs amp_snake -> the polyphase transposed conv of amp_conv_create(transposed = 1, ...) (bit for bit that sequence when
+ * output_padding == 0) with a workspace of amp_tconv_workspace_bytes (one [B, cin, T] tensor; unused when alpha_dev is NULL).  The f16x3 forms
+ * feed the op-level range flag (amp_range_check).  Limits at forward: T_out <= 0 is AMP_ERR_INVALID; T_out > 2^30, or a fused grid of
+ * B * ceil((T + 1) / 64) >= 2^31 workgroups, AMP_ERR_UNSUPPORTED.  y_dev must not alias x_dev.  Deterministic; an item never depends on its batch. */
+typedef struct amp_tconv amp_tconv;
+int amp_tconv_create(int cin, int cout, int stride, int padding, int output_padding, const float* weight_host, const float* bias_host,
+                     amp_tconv** out);
+int amp_tconv_out_len(const amp_tconv* h, int T);
+int amp_tconv_fused(const amp_tconv* h);
+/* Which route handles created AFTER the call take: -1 (default) the policy above, 0 the two launches everywhere, 1 the fused launch wherever it
+ * is built -- an A/B switch for tools/dac_bench.py and the tests. */
+int amp_set_tconv_fusion(int mode);
+size_t amp_tconv_workspace_bytes(const amp_tconv* h, int B, int T);
+int amp_tconv_forward(const amp_tconv* h, const float* x_dev, int B, int T, const float* alpha_dev, void* ws_dev, size_t ws_bytes, float* y_dev,
+                      void* stream);
+void amp_tconv_destroy(amp_tconv* h);
 
 #ifdef __cplusplus
 }
