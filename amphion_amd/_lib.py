@@ -145,6 +145,10 @@ _SIGNATURES = {
     "amp_fvq_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "amp_fvq_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "amp_fvq_check": (c_int, [c_void_p, c_void_p]),
+    "amp_fvq_encode_ex": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "amp_fvq_decode_add": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "amp_semantic_prepare": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "amp_fvq_destroy": (None, [c_void_p]),
     "amp_codec_unit_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "amp_codec_unit_fused": (c_int, [c_void_p]),
@@ -170,6 +174,8 @@ _SIGNATURES = {
     "amp_dds_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float,
                              c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "amp_dwconv_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "amp_dwconv_layer_norm_c_causal": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                               c_void_p, c_void_p]),
     "amp_rel_attention_strided": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "amp_set_rel_attention_tiled": (c_int, [c_int]),
     "amp_set_resblock_streams": (c_int, [c_int]),

@@ -1,6 +1,9 @@
 // Residual factorized vector quantizer of the Amphion acoustic codec in eval mode (models/codec/amphion_codec/quantize/residual_vq.py:68-152,
 // factorized_vector_quantize.py:52-127; quantizer_type "fvq"): amp_fvq_encode = ResidualVQ.forward (codes + quantized_out) in ONE launch,
-// amp_fvq_decode = ResidualVQ.vq2emb.
+// amp_fvq_decode = ResidualVQ.vq2emb.  amp_fvq_encode_ex / amp_fvq_decode_add are the same two kernels with DualCodec's DAC.encode /
+// DAC.decode_from_codes folded in (model_codec/dac_model.py:301-312,319-320): z read as the crop [..., :T] of a longer tensor, the residual
+// started as z - sub, quantized_out stored as sum z_q + sub, every level's z_e stored as `latents`; decode stores sum + add.  Each of the
+// folded operations is ONE fp32 add or subtract of two stored values -- the bits of torch's separate passes.
 //
 // Everything here decides or reproduces INTEGERS, so it is plain fp32 on the vector ALU -- no f16x3, no MFMA.  A workgroup of 256 threads owns
 // FVQ_TF = 16 frames of one item and keeps their residual [D][16] and the running sum of the levels' z_q [D][16] in LDS across all levels:
@@ -28,7 +31,9 @@ namespace amp {
 constexpr int FVQ_TF = 16;
 
 struct FvqArgs {
-    const float* z;          // [B, D, T]
+    const float* z;          // [B, D, zT], columns [0, T) read
+    const float* sub;        // [B, D, T] or nullptr: the residual starts as z - sub, zq receives the sum + sub
+    float* lat;              // [B, n * d, T] every level's z_e (torch.cat(latents, 1)) or nullptr
     long long* codes;        // [n, B, T]
     float* zq;               // [B, D, T] or nullptr
     float* allq;             // [n, B, D, T] every level's z_q (ResidualVQ.forward's all_quantized) or nullptr
@@ -41,6 +46,7 @@ struct FvqArgs {
     const float* b_out;      // [N][D]
     int B, D, d, K, T, n, l2;
     int tiles_per_item;
+    long long zT;            // row stride of z (>= T)
 };
 
 template <int DP>
@@ -66,10 +72,13 @@ __global__ __launch_bounds__(256) void fvq_encode_kernel(const FvqArgs a) {
     const int t0 = (blockIdx.x - item * a.tiles_per_item) * FVQ_TF;
     const int t = t0 + f;
     const bool tok = t < T;
-    const float* zb = a.z + (size_t)item * D * T;
+    const float* zb = a.z + (size_t)item * D * a.zT;
+    const float* sb = a.sub ? a.sub + (size_t)item * D * T : nullptr;
 
     for (int c = part16; c < D; c += 16) {
-        R[c * FVQ_TF + f] = tok ? zb[(size_t)c * T + t] : 0.f;
+        float r = tok ? zb[(size_t)c * a.zT + t] : 0.f;
+        if (sb && tok) r -= sb[(size_t)c * T + t];
+        R[c * FVQ_TF + f] = r;
         Q[c * FVQ_TF + f] = 0.f;
     }
     for (int i = tid; i < DP * FVQ_TF; i += 256) { E[i] = 0.f; EN[i] = 0.f; }
@@ -160,6 +169,7 @@ __global__ __launch_bounds__(256) void fvq_encode_kernel(const FvqArgs a) {
             const int j = i / FVQ_TF, ff = i - j * FVQ_TF;
             const float ze = E[i];
             EN[i] = ze + (a.cb[((size_t)l * K + CODE[ff]) * DP + j] - ze);
+            if (a.lat && t0 + ff < T) a.lat[(((size_t)item * a.n + l) * d + j) * T + t0 + ff] = ze;
         }
         __syncthreads();
         // ---- out_project, residual and sum ----
@@ -186,13 +196,18 @@ __global__ __launch_bounds__(256) void fvq_encode_kernel(const FvqArgs a) {
     }
     if (a.zq && tok) {
         float* qb = a.zq + (size_t)item * D * T;
-        for (int c = part16; c < D; c += 16) qb[(size_t)c * T + t] = Q[c * FVQ_TF + f];
+        if (sb) {
+            for (int c = part16; c < D; c += 16) qb[(size_t)c * T + t] = Q[c * FVQ_TF + f] + sb[(size_t)c * T + t];
+        } else {
+            for (int c = part16; c < D; c += 16) qb[(size_t)c * T + t] = Q[c * FVQ_TF + f];
+        }
     }
 }
 
 struct FvqDecArgs {
     const long long* codes;  // [n, B, T]
     float* out;              // [B, D, T]
+    const float* add;        // [B, D, T] or nullptr: out = sum + add
     const float* cb;         // [N][K][DP]
     const float* w_out;      // [N][D][d] or nullptr
     const float* b_out;      // [N][D]
@@ -229,6 +244,7 @@ __global__ __launch_bounds__(256) void fvq_decode_kernel(const FvqDecArgs a) {
     __syncthreads();
     if (t >= T) return;
     float* ob = a.out + (size_t)item * D * T;
+    const float* ab = a.add ? a.add + (size_t)item * D * T : nullptr;
     for (int c = part16; c < D; c += 16) {
         float acc = 0.f;
         for (int l = 0; l < n; ++l) {
@@ -244,7 +260,7 @@ __global__ __launch_bounds__(256) void fvq_decode_kernel(const FvqDecArgs a) {
             }
             acc = l ? acc + s : s;
         }
-        ob[(size_t)c * T + t] = acc;
+        ob[(size_t)c * T + t] = ab ? acc + ab[(size_t)c * T + t] : acc;
     }
 }
 
@@ -345,13 +361,14 @@ static int fvq_check_shape(const amp_fvq* h, int n_quantizers, int B, int T, con
     return AMP_OK;
 }
 
-int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_quantizers, long long* codes_dev, float* zq_dev, float* all_zq_dev,
-                   void* stream) {
-    AMP_RC(fvq_check_shape(h, n_quantizers, B, T, "amp_fvq_encode"));
-    if (!z_dev || !codes_dev) { set_error("amp_fvq_encode: null argument"); return AMP_ERR_INVALID; }
-    if (z_dev == zq_dev) { set_error("amp_fvq_encode: z and zq must not alias"); return AMP_ERR_INVALID; }
+static int fvq_encode_run(const char* who, const amp_fvq* h, const float* z_dev, long long z_row_stride, const float* sub_dev, int B, int T,
+                          int n_quantizers, long long* codes_dev, float* zq_dev, float* all_zq_dev, float* latents_dev, void* stream) {
+    AMP_RC(fvq_check_shape(h, n_quantizers, B, T, who));
+    if (!z_dev || !codes_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
+    if (z_dev == zq_dev) { set_error("%s: z and zq must not alias", who); return AMP_ERR_INVALID; }
+    if (z_row_stride < T) { set_error("%s: z row stride %lld is shorter than T = %d", who, z_row_stride, T); return AMP_ERR_INVALID; }
     FvqArgs a{};
-    a.z = z_dev; a.codes = codes_dev; a.zq = zq_dev; a.allq = all_zq_dev;
+    a.z = z_dev; a.codes = codes_dev; a.zq = zq_dev; a.allq = all_zq_dev; a.sub = sub_dev; a.lat = latents_dev; a.zT = z_row_stride;
     a.w_in = h->w_in; a.b_in = h->b_in; a.cb = h->cb; a.cbn = h->cbn; a.cn2 = h->cn2; a.w_out = h->w_out; a.b_out = h->b_out;
     a.B = B; a.D = h->D; a.d = h->d; a.K = h->K; a.T = T; a.n = n_quantizers; a.l2 = h->l2;
     a.tiles_per_item = (T + FVQ_TF - 1) / FVQ_TF;
@@ -359,7 +376,8 @@ int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_qua
     const size_t lds = fvq_lds_bytes(h->D, h->DP);
     const double frames = (double)B * T;
     const double gf = frames * n_quantizers * (2.0 * h->d * h->D * (h->proj ? 2 : 0) + 2.0 * h->K * h->d) / 1e9;
-    const double mb = (frames * h->D * 4.0 * (1 + (zq_dev ? 1 : 0) + (all_zq_dev ? n_quantizers : 0)) + frames * n_quantizers * 8.0) / 1e6;
+    const double mb = (frames * h->D * 4.0 * (1 + (sub_dev ? (zq_dev ? 2 : 1) : 0) + (zq_dev ? 1 : 0) + (all_zq_dev ? n_quantizers : 0)) +
+                       frames * n_quantizers * (8.0 + (latents_dev ? 4.0 * h->d : 0.0))) / 1e6;
     note_kernel("fvq_encode_kernel", h->DP);
     note_work(grid, gf, mb, "fvq encode D=%d d=%d K=%d n=%d T=%d B=%d", h->D, h->d, h->K, n_quantizers, T, B);
     hipStream_t st = (hipStream_t)stream;
@@ -377,23 +395,46 @@ int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_qua
     return AMP_OK;
 }
 
-int amp_fvq_decode(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, float* out_dev, void* stream) {
-    AMP_RC(fvq_check_shape(h, n_quantizers, B, T, "amp_fvq_decode"));
-    if (!codes_dev || !out_dev) { set_error("amp_fvq_decode: null argument"); return AMP_ERR_INVALID; }
+int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_quantizers, long long* codes_dev, float* zq_dev, float* all_zq_dev,
+                   void* stream) {
+    return fvq_encode_run("amp_fvq_encode", h, z_dev, T, nullptr, B, T, n_quantizers, codes_dev, zq_dev, all_zq_dev, nullptr, stream);
+}
+
+int amp_fvq_encode_ex(const amp_fvq* h, const float* z_dev, long long z_row_stride, const float* sub_dev, int B, int T, int n_quantizers,
+                      long long* codes_dev, float* zq_dev, float* all_zq_dev, float* latents_dev, void* stream) {
+    if (sub_dev && sub_dev == zq_dev) { set_error("amp_fvq_encode_ex: sub and zq must not alias"); return AMP_ERR_INVALID; }
+    return fvq_encode_run("amp_fvq_encode_ex", h, z_dev, z_row_stride, sub_dev, B, T, n_quantizers, codes_dev, zq_dev, all_zq_dev, latents_dev,
+                          stream);
+}
+
+static int fvq_decode_run(const char* who, const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, const float* add_dev,
+                          float* out_dev, void* stream) {
+    AMP_RC(fvq_check_shape(h, n_quantizers, B, T, who));
+    if (!codes_dev || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
     FvqDecArgs a{};
-    a.codes = codes_dev; a.out = out_dev; a.cb = h->cb; a.w_out = h->w_out; a.b_out = h->b_out; a.flag = h->flag;
+    a.codes = codes_dev; a.out = out_dev; a.add = add_dev; a.cb = h->cb; a.w_out = h->w_out; a.b_out = h->b_out; a.flag = h->flag;
     a.B = B; a.D = h->D; a.d = h->d; a.DP = h->DP; a.K = h->K; a.T = T; a.n = n_quantizers;
     a.tiles_per_item = (T + FVQ_TF - 1) / FVQ_TF;
     const unsigned grid = (unsigned)((size_t)B * a.tiles_per_item);
     const double frames = (double)B * T;
     note_kernel("fvq_decode_kernel");
-    note_work(grid, frames * n_quantizers * 2.0 * h->d * h->D * (h->proj ? 1 : 0) / 1e9, (frames * h->D * 4.0 + frames * n_quantizers * 8.0) / 1e6,
+    note_work(grid, frames * n_quantizers * 2.0 * h->d * h->D * (h->proj ? 1 : 0) / 1e9,
+              (frames * h->D * 4.0 * (add_dev ? 2 : 1) + frames * n_quantizers * 8.0) / 1e6,
               "fvq decode D=%d d=%d K=%d n=%d T=%d B=%d", h->D, h->d, h->K, n_quantizers, T, B);
     const size_t lds = ((size_t)n_quantizers * h->d + n_quantizers) * FVQ_TF * sizeof(float);
     AMP_HIP(ensure_dynamic_lds<&fvq_decode_kernel>(lds));
     hipLaunchKernelGGL(fvq_decode_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
     AMP_HIP(hipGetLastError());
     return AMP_OK;
+}
+
+int amp_fvq_decode(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, float* out_dev, void* stream) {
+    return fvq_decode_run("amp_fvq_decode", h, codes_dev, n_quantizers, B, T, nullptr, out_dev, stream);
+}
+
+int amp_fvq_decode_add(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, const float* add_dev, float* out_dev,
+                       void* stream) {
+    return fvq_decode_run("amp_fvq_decode_add", h, codes_dev, n_quantizers, B, T, add_dev, out_dev, stream);
 }
 
 int amp_fvq_check(amp_fvq* h, void* stream) {

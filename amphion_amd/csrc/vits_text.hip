@@ -45,9 +45,12 @@ __device__ __forceinline__ float ln_affine(float v, float mu, float rstd, float 
 //         themselves (amp_conv_forward_ragged) and whatever they leave beyond an utterance's end stops here;
 //   DWK   the depthwise dilated conv of DDSConv (modules/flow/modules.py:63-64: norm_1(conv_sep(x * mask))) evaluated on load:
 //         value(c, t) = bias[c] + sum_j w[c, j] * xm[c, t - pad + j * dil] in the tap order of dwconv_kernel (same bits).
+//   CAUSAL the same prologue with all of the padding on the left (pad = (DWK - 1) * dil, none on the right): the causal ConvNeXt block
+//         of DualCodec (model_codec/cnn.py:85-93, F.pad(x, (6, 0)) -> dwconv(padding = 0) -> LayerNorm).  Only the tap columns move:
+//         the same bits as the centred form run on a copy of x left-padded by pad zeros, read pad / 2 columns later.
 constexpr int LN_TT = 32, LN_G = 8, LN_DW_MAXC = 1024;   // NC = channels per thread held in registers: 24 (C <= 192) or 32
 #define NTAP_(k) ((k) > 0 ? (k) : 1)
-template <int DWK, int NC>
+template <int DWK, int NC, int CAUSAL = 0>
 __global__ __launch_bounds__(256) void layer_norm_c_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ post,
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(256) void layer_norm_c_kernel(const float* __restri
     bool tv[NTAP];
 #pragma unroll
     for (int j = 0; j < NTAP; ++j) {
-        const int u = DWK > 0 ? t - (DWK * dil - dil) / 2 + j * dil : t;
+        const int u = DWK > 0 ? t - (CAUSAL ? DWK * dil - dil : (DWK * dil - dil) / 2) + j * dil : t;
         tv[j] = u >= 0 && u < (DWK > 0 ? len : T);
         tu[j] = u < 0 ? 0 : (u > T - 1 ? T - 1 : u);
     }
@@ -923,7 +926,7 @@ extern "C" {
 
 static int layer_norm_run(const char* who, const float* x_dev, const float* res_dev, const float* gamma_dev, const float* beta_dev,
                           const float* post_dev, const int* lens_dev, const float* dw_w, const float* dw_b, int K, int dil, int B, int C,
-                          int T, float eps, int gelu, float* y_dev, void* stream) {
+                          int T, float eps, int gelu, float* y_dev, void* stream, int causal = 0) {
     VT_CHECK(x_dev && gamma_dev && beta_dev && y_dev && B > 0 && C > 0 && T > 0 && B <= 65535, "%s: bad argument", who);
     VT_CHECK(x_dev != y_dev || !dw_w, "%s: the depthwise prologue reads neighbouring columns: y must not alias x", who);
     const dim3 grid((T + LN_TT - 1) / LN_TT, B);
@@ -935,7 +938,8 @@ static int layer_norm_run(const char* who, const float* x_dev, const float* res_
     } else {
         VT_CHECK((K == 3 || K == 7) && dil > 0 && C <= LN_DW_MAXC, "%s: the fused depthwise prologue covers K = 3 or 7, C <= %d (got K=%d dilation=%d C=%d): run amp_dwconv first", who, LN_DW_MAXC, K, dil, C);
         // K = 7 (ConvNeXt's dwconv, vocos.py:489-496): 16 channels per thread in registers -- 7 taps of 32 would not fit the VGPR file
-        auto kern = K == 7 ? layer_norm_c_kernel<7, 16> : nc24 ? layer_norm_c_kernel<3, 24> : layer_norm_c_kernel<3, 32>;
+        VT_CHECK(!causal || (K == 7 && dil == 1), "%s: the causal prologue covers K = 7, dilation 1 (got K=%d dilation=%d)", who, K, dil);
+        auto kern = causal ? layer_norm_c_kernel<7, 16, 1> : K == 7 ? layer_norm_c_kernel<7, 16> : nc24 ? layer_norm_c_kernel<3, 24> : layer_norm_c_kernel<3, 32>;
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, x_dev,
                            res_dev, gamma_dev, beta_dev, post_dev, lens_dev, dw_w, dw_b, dil, y_dev, C, T, eps, gelu);
     }
@@ -980,6 +984,14 @@ int amp_dwconv_layer_norm_c(const float* x_dev, const float* dw_weight_dev, cons
     VT_CHECK(dw_weight_dev, "amp_dwconv_layer_norm_c: null depthwise weight");
     return layer_norm_run("amp_dwconv_layer_norm_c", x_dev, nullptr, gamma_dev, beta_dev, nullptr, lens_dev, dw_weight_dev, dw_bias_dev, K,
                           dilation, B, C, T, eps, gelu, y_dev, stream);
+}
+
+int amp_dwconv_layer_norm_c_causal(const float* x_dev, const float* dw_weight_dev, const float* dw_bias_dev, int K, int dilation,
+                                   const float* gamma_dev, const float* beta_dev, const int* lens_dev, int B, int C, int T, float eps,
+                                   int gelu, float* y_dev, void* stream) {
+    VT_CHECK(dw_weight_dev, "amp_dwconv_layer_norm_c_causal: null depthwise weight");
+    return layer_norm_run("amp_dwconv_layer_norm_c_causal", x_dev, nullptr, gamma_dev, beta_dev, nullptr, lens_dev, dw_weight_dev, dw_bias_dev,
+                          K, dilation, B, C, T, eps, gelu, y_dev, stream, 1);
 }
 
 static int rel_attention_run(const char* who, const float* q_dev, const float* k_dev, const float* v_dev, long long bs, const float* emb_k_dev,

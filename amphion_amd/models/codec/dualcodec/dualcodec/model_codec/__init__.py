@@ -1,3 +1,7 @@
-"""DualCodec's DAC encoder / decoder stacks (models/codec/dualcodec/dualcodec/model_codec/dac_model.py:49-169) on the gfx950 kernels.  The DAC and
-DualCodec model classes, their quantizers and the semantic branch are not on the HIP path."""
-from .dac_model import Decoder, DecoderBlock, Encoder, EncoderBlock, ResidualUnit  # noqa: F401
+"""DualCodec (models/codec/dualcodec/dualcodec/model_codec/) in eval mode on the gfx950 kernels: the DAC encoder / decoder stacks, the DAC
+residual quantizer, the (causal) ConvNeXt block, and the ``DAC`` and ``DualCodec`` models with ``encode`` / ``decode_from_codes``.  Not here:
+``get_model`` and the hydra configs, checkpoint download, w2v-BERT itself, resampling and the TTS models under ``model_tts/``."""
+from .cnn import ConvNeXtBlock  # noqa: F401
+from .dac_model import DAC, AttrDict, Decoder, DecoderBlock, Encoder, EncoderBlock, ResidualUnit  # noqa: F401
+from .dac_quantize import ResidualVectorQuantize, VectorQuantize  # noqa: F401
+from .dualcodec_model import DualCodec, prepare_semantic_features  # noqa: F401

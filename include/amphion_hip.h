@@ -95,7 +95,8 @@ typedef struct amp_gen amp_gen;
  * powers of two keep their kernels); 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision /
  * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024); 144 (additive): the DiffWave entry
  * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*;
- * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion. */
+ * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
+ * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -257,6 +258,13 @@ int amp_layer_norm_c_ragged(const float* x_dev, const float* res_dev, const floa
 int amp_dwconv_layer_norm_c(const float* x_dev, const float* dw_weight_dev, const float* dw_bias_dev, int K, int dilation,
                             const float* gamma_dev, const float* beta_dev, const int* lens_dev, int B, int C, int T, float eps,
                             int gelu, float* y_dev, void* stream);
+/* amp_dwconv_layer_norm_c with ALL of the depthwise padding on the left: y[t] = act(LN(b + sum_j w[j] x[t - (K - 1) + j])), the causal
+ * ConvNeXt block of DualCodec (model_codec/cnn.py:85-93: F.pad(x, (6, 0)) -> dwconv(padding = 0) -> LayerNorm) in one launch.  Covered:
+ * K = 7, dilation 1, C <= 1024; anything else AMP_ERR_INVALID.  Same arguments, same tap order: bit-identical to amp_dwconv_layer_norm_c
+ * run on a copy of x left-padded by 6 zeros and read at columns t + 3.  y != x. */
+int amp_dwconv_layer_norm_c_causal(const float* x_dev, const float* dw_weight_dev, const float* dw_bias_dev, int K, int dilation,
+                                   const float* gamma_dev, const float* beta_dev, const int* lens_dev, int B, int C, int T, float eps,
+                                   int gelu, float* y_dev, void* stream);
 /* The seam between DDSConv layers i and i + 1 (modules/flow/modules.py:63-70) in one launch:
  *     x_out = x + gelu(LN(y; gamma2, beta2))                    norms_2[i] on the 1 x 1 conv's output y, residual x
  *     z_out = gelu(LN(dwconv(x_out * mask); gamma1, beta1))     convs_sep[i+1] -> norms_1[i+1]
@@ -660,6 +668,25 @@ int amp_fvq_encode(const amp_fvq* h, const float* z_dev, int B, int T, int n_qua
 int amp_fvq_decode(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, float* out_dev, void* stream);
 int amp_fvq_check(amp_fvq* h, void* stream);
 void amp_fvq_destroy(amp_fvq* h);
+/* The same two launches with DualCodec's DAC.encode / DAC.decode_from_codes folded in (model_codec/dac_model.py:301-312,319-320).
+ * amp_fvq_encode_ex: z is read as columns [0, T) of a [B, D, z_row_stride] tensor (z_row_stride >= T, else AMP_ERR_INVALID: the crop
+ *   z[..., :T]); sub_dev [B, D, T] not NULL: the residual starts as z - sub and zq_dev receives (sum of the levels' z_q) + sub; latents_dev
+ *   [B, n_quantizers * d, T] not NULL receives every level's z_e = in_project(residual) (torch.cat(latents, 1)); all_zq_dev as in
+ *   amp_fvq_encode (level 0 = z_q_1).  sub must not alias zq.  With sub_dev = latents_dev = NULL and z_row_stride = T it IS amp_fvq_encode;
+ *   with sub_dev set, codes / zq are bit for bit those of (z[..., :T] - sub) -> amp_fvq_encode -> (zq + sub) done as separate fp32 passes.
+ * amp_fvq_decode_add: out = amp_fvq_decode(codes) + add (add_dev [B, D, T]; NULL: amp_fvq_decode itself), bit for bit the separate add. */
+int amp_fvq_encode_ex(const amp_fvq* h, const float* z_dev, long long z_row_stride, const float* sub_dev, int B, int T, int n_quantizers,
+                      long long* codes_dev, float* zq_dev, float* all_zq_dev, float* latents_dev, void* stream);
+int amp_fvq_decode_add(const amp_fvq* h, const long long* codes_dev, int n_quantizers, int B, int T, const float* add_dev, float* out_dev,
+                       void* stream);
+
+/* The feature preparation in front of DualCodec's semantic branch (infer/dualcodec/inference_with_semantic.py:155-164,232):
+ * hidden [B, T, C] time-major -> out [B, C, floor(T / factor)] = avg_pool1d(((hidden - mean) / std).transpose(1, 2), factor, factor).
+ * mean_dev / std_dev [C]; either may be NULL to skip that step.  fp32 in this order per output element: subtract, divide, the `factor`
+ * terms summed in ascending time order, then times 1 / factor.  The last T mod factor frames are not read.  factor >= 1; T < factor is
+ * AMP_ERR_INVALID; B or ceil(C / 64) beyond 65535 AMP_ERR_UNSUPPORTED.  out must not alias hidden. */
+int amp_semantic_prepare(const float* hidden_dev, const float* mean_dev, const float* std_dev, int B, int T, int C, int factor, float* out_dev,
+                         void* stream);
 
 /* ResidualUnit of the codec encoder (codec.py:60-76): y = x + conv1x1(snake_2(conv7(snake_1(x)))), Snake1d as codec.py:34-39
  * (x + (alpha + 1e-9)^-1 sin^2(alpha x)), conv7 = Conv1d(C, C, 7, dilation, padding 3 * dilation).  alpha*_host [C], w1_host [C, C, 7] and
