@@ -156,6 +156,13 @@ _SIGNATURES = {
     "amp_codec_unit_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "amp_codec_unit_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "amp_codec_unit_destroy": (None, [c_void_p]),
+    "amp_aa_unit_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, POINTER(c_void_p)]),
+    "amp_aa_unit_fused": (c_int, [c_void_p]),
+    "amp_set_aa_unit_fusion": (c_int, [c_int]),
+    "amp_aa_unit_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_aa_unit_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_aa_unit_destroy": (None, [c_void_p]),
     "amp_sconv_create": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
     "amp_sconv_out_len": (c_int, [c_void_p, c_int]),
     "amp_sconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),

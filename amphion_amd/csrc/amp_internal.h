@@ -204,6 +204,26 @@ struct CodecUnitArgs {
 size_t codec_unit_lds_bytes(int C, int d);
 hipError_t launch_codec_unit(CodecUnitArgs a, int B, hipStream_t stream);
 
+// Arguments of FACodec's fused anti-aliased residual unit (aa_unit_f16x3.hip): ResidualUnit with Activation1d(Snake | SnakeBeta) in one launch
+constexpr int AA_N1 = 64;   // columns of GEMM 1 per workgroup ...
+constexpr int AA_TN = 54;   // ... of which the inner AA_N1 - 2 * 5 are output columns (Activation1d reaches 5 columns either way)
+struct AaUnitArgs {
+    const float* x;            // [B, C, T] input and residual
+    float* y;                  // [B, C, T]; must NOT alias x (other tiles read x's halo)
+    const uint4* wp1;          // [C, 7 C] (tap-major K) as packed A fragments
+    const uint4* wp2;          // [C, C]
+    const float* bias1;        // [C]
+    const float* bias2;        // [C]
+    const float *a1, *invb1, *a2, *invb2;   // Activation1d of each conv's input: alpha (exp'ed when logscale) and 1 / (beta + 1e-9), [C]
+    const float* filt;         // 12 up-sampling taps (without UpSample1d's gain of 2), 12 down-sampling taps
+    int C, T, d;
+    int tiles_per_item;        // set by the launcher
+    float inv1, inv2;          // 1 / (16 * 2^s) of each matrix
+    unsigned* range_flag;      // see ConvArgs
+};
+size_t aa_unit_lds_bytes(int C, int d);
+hipError_t launch_aa_unit(AaUnitArgs a, int B, hipStream_t stream);
+
 // Arguments of the fused Snake -> ConvTranspose1d(k = 2 s, stride s) kernel (tconv_f16x3.hip): the decoder blocks' up-sampling step in one launch
 constexpr int TC_TN = 64;   // GEMM columns q (input positions) per workgroup
 struct TconvArgs {

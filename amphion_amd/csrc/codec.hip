@@ -2,7 +2,8 @@
 // (amp_codec_unit_*: the fused kernel of codec_unit_f16x3.hip where it is built, else the four launches it replaces) and the strided
 // down-sampling conv (amp_sconv_*: Snake + space-to-depth in one small kernel, then a k = 2 conv on the implicit-GEMM kernels); and of the
 // decoder blocks' up-sampling step (amp_tconv_*: Snake + ConvTranspose1d(k = 2 s, stride s) as the fused kernel of tconv_f16x3.hip where it is
-// built, else amp_snake -> the polyphase transposed conv).
+// built, else amp_snake -> the polyphase transposed conv); and of FACodec's residual unit (amp_aa_unit_*: the same unit with Activation1d in
+// place of Snake1d, the fused kernel of aa_unit_f16x3.hip where it is built, else act1d -> conv -> act1d -> conv).
 #include <memory>
 
 #include "act1d_math.h"
@@ -52,6 +53,25 @@ struct amp_codec_unit {
     float *b1 = nullptr, *b2 = nullptr, *al1 = nullptr, *ib1 = nullptr, *al2 = nullptr, *ib2 = nullptr;
     float inv1 = 1.f, inv2 = 1.f;
     std::unique_ptr<amp_conv> c1, c2;     // the unfused route
+    DeviceAllocs dev;
+};
+
+// amp_set_aa_unit_fusion: -1 the measured policy, 0 never (the four launches), 1 wherever the fused kernel is built.  Read at create time.
+static int g_aa_unit_fusion = -1;
+// the widths the policy hands to the fused kernel: none.  Measured (B = 16, both routes through amp_aa_unit_forward as captured
+// graphs, alternating): C = 32 fused 1.02 - 1.20 ms vs 0.69, C = 64 2.04 - 2.62 vs 1.47, C = 128 4.00 - 4.18 vs 1.80 -- the fused kernel is
+// VALU-bound on its two activations and loses at every width
+static bool aa_unit_policy_fused(int C) { (void)C; return false; }
+
+struct amp_aa_unit {
+    int C = 0, d = 1, precision = PREC_F16X3;
+    bool fused = false;
+    uint4 *wp1 = nullptr, *wp2 = nullptr;
+    float *b1 = nullptr, *b2 = nullptr;
+    float inv1 = 1.f, inv2 = 1.f;
+    float *a1 = nullptr, *ib1 = nullptr, *a2 = nullptr, *ib2 = nullptr;   // alpha (exp'ed when logscale), 1 / (beta + 1e-9)
+    float* filt = nullptr;                // 12 up taps, 12 down taps
+    std::unique_ptr<amp_conv> c1, c2;     // the four-launch route
     DeviceAllocs dev;
 };
 
@@ -176,6 +196,110 @@ int amp_codec_unit_forward(const amp_codec_unit* h, const float* x_dev, int B, i
 }
 
 void amp_codec_unit_destroy(amp_codec_unit* h) { delete h; }
+
+int amp_aa_unit_create(int channels, int dilation, const float* alpha1_host, const float* beta1_host, const float* w1_host, const float* b1_host,
+                       const float* alpha2_host, const float* beta2_host, const float* w2_host, const float* b2_host, int logscale,
+                       const float* filt_up_host, const float* filt_down_host, amp_aa_unit** out) {
+    if (!alpha1_host || !w1_host || !b1_host || !alpha2_host || !w2_host || !b2_host || !filt_up_host || !filt_down_host || !out) {
+        set_error("amp_aa_unit_create: null argument");
+        return AMP_ERR_INVALID;
+    }
+    if (amp_device_count() <= 0) { set_error("amp_aa_unit_create: no HIP device visible (the HIP path has no CPU fallback)"); return AMP_ERR_HIP; }
+    const int C = channels, d = dilation;
+    if (C < 1 || d < 1) { set_error("amp_aa_unit_create: C=%d dilation=%d", C, d); return AMP_ERR_INVALID; }
+    auto h = std::make_unique<amp_aa_unit>();
+    h->C = C; h->d = d; h->precision = default_precision();
+    const bool built = h->precision == PREC_F16X3 && C % 32 == 0 && C <= 128 && d <= 9;
+    h->fused = built && g_aa_unit_fusion != 0 && (g_aa_unit_fusion == 1 || aa_unit_policy_fused(C));
+    // a = alpha, 1 / (beta + 1e-9) with beta = alpha for plain Snake, both exp'ed first when logscale: act_params_upload's expressions
+    std::vector<float> a1(C), ib1(C), a2(C), ib2(C), filt(24);
+    for (int c = 0; c < C; ++c) {
+        float av = alpha1_host[c], bv = beta1_host ? beta1_host[c] : alpha1_host[c];
+        if (logscale) { av = expf(av); bv = expf(bv); }
+        a1[c] = av; ib1[c] = 1.0f / (bv + 0.000000001f);
+        av = alpha2_host[c]; bv = beta2_host ? beta2_host[c] : alpha2_host[c];
+        if (logscale) { av = expf(av); bv = expf(bv); }
+        a2[c] = av; ib2[c] = 1.0f / (bv + 0.000000001f);
+    }
+    for (int i = 0; i < 12; ++i) { filt[i] = filt_up_host[i]; filt[12 + i] = filt_down_host[i]; }
+    AMP_RC(h->dev.upload(a1, &h->a1));
+    AMP_RC(h->dev.upload(ib1, &h->ib1));
+    AMP_RC(h->dev.upload(a2, &h->a2));
+    AMP_RC(h->dev.upload(ib2, &h->ib2));
+    AMP_RC(h->dev.upload(filt, &h->filt));
+    if (h->fused) {
+        AMP_RC(h->dev.upload(b1_host, sizeof(float) * C, (void**)&h->b1));
+        AMP_RC(h->dev.upload(b2_host, sizeof(float) * C, (void**)&h->b2));
+        std::vector<_Float16> p1, p2;
+        float inv1 = 1.f, inv2 = 1.f;
+        if (int rc = pack_matrix_f16x3("amp_aa_unit_create", C, 7 * C, C / 32, 7 * C / 16,
+                                       [&](int m, int i) { const int tap = i / C, c = i - tap * C; return w1_host[((size_t)m * C + c) * 7 + tap]; }, &p1, &inv1);
+            rc != AMP_OK) return rc;
+        if (int rc = pack_matrix_f16x3("amp_aa_unit_create", C, C, C / 32, C / 16, [&](int m, int i) { return w2_host[(size_t)m * C + i]; }, &p2, &inv2);
+            rc != AMP_OK) return rc;
+        h->inv1 = inv1; h->inv2 = inv2;
+        AMP_RC(h->dev.upload(p1, &h->wp1));
+        AMP_RC(h->dev.upload(p2, &h->wp2));
+    } else {
+        for (size_t i = 0; i < (size_t)C * C * 7; ++i)
+            if (!(fabsf(w1_host[i]) < 1e30f)) { set_error("amp_aa_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
+        for (size_t i = 0; i < (size_t)C * C; ++i)
+            if (!(fabsf(w2_host[i]) < 1e30f)) { set_error("amp_aa_unit_create: non-finite weight"); return AMP_ERR_INVALID; }
+        h->c1 = std::make_unique<amp_conv>();
+        h->c1->cin = C; h->c1->cout = C; h->c1->k = 7; h->c1->dilation = d; h->c1->padding = 3 * d;
+        AMP_RC(conv_build(h->c1.get(), w1_host, b1_host));
+        h->c2 = std::make_unique<amp_conv>();
+        h->c2->cin = C; h->c2->cout = C; h->c2->k = 1;
+        AMP_RC(conv_build(h->c2.get(), w2_host, b2_host));
+    }
+    *out = h.release();
+    return AMP_OK;
+}
+
+int amp_set_aa_unit_fusion(int mode) {
+    if (mode < -1 || mode > 1) { set_error("amp_set_aa_unit_fusion: mode %d (-1 policy, 0 off, 1 wherever built)", mode); return AMP_ERR_INVALID; }
+    g_aa_unit_fusion = mode;
+    return AMP_OK;
+}
+
+int amp_aa_unit_fused(const amp_aa_unit* h) { return h ? (h->fused ? 1 : 0) : -1; }
+
+size_t amp_aa_unit_workspace_bytes(const amp_aa_unit* h, int B, int T) {
+    if (!h || h->fused || B <= 0 || T <= 0) return 0;
+    return (size_t)2 * B * h->C * T * sizeof(float);
+}
+
+int amp_aa_unit_forward(const amp_aa_unit* h, const float* x_dev, int B, int T, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream_) {
+    if (!h || !x_dev || !y_dev) { set_error("amp_aa_unit_forward: null argument"); return AMP_ERR_INVALID; }
+    if (B <= 0 || T <= 0) { set_error("amp_aa_unit_forward: B=%d T=%d", B, T); return AMP_ERR_INVALID; }
+    if (x_dev == y_dev) { set_error("amp_aa_unit_forward: x and y must not alias (the conv reads a halo)"); return AMP_ERR_INVALID; }
+    hipStream_t st = (hipStream_t)stream_;
+    if (h->fused) {
+        // the kernel forms 2 T (the last Snake index) as an int
+        if (T > (1 << 29) || (long long)B * ((T + AA_TN - 1) / AA_TN) > 0x7fffffffll) {
+            set_error("amp_aa_unit_forward: B=%d x T=%d is beyond the kernel's index arithmetic", B, T);
+            return AMP_ERR_UNSUPPORTED;
+        }
+        AaUnitArgs a{};
+        a.x = x_dev; a.y = y_dev; a.wp1 = h->wp1; a.wp2 = h->wp2; a.bias1 = h->b1; a.bias2 = h->b2;
+        a.a1 = h->a1; a.invb1 = h->ib1; a.a2 = h->a2; a.invb2 = h->ib2; a.filt = h->filt;
+        a.C = h->C; a.T = T; a.d = h->d; a.inv1 = h->inv1; a.inv2 = h->inv2;
+        a.range_flag = range_flag_for_current_device();
+        AMP_HIP(launch_aa_unit(a, B, st));
+        return AMP_OK;
+    }
+    const size_t need = amp_aa_unit_workspace_bytes(h, B, T);
+    if (!ws_dev || ws_bytes < need) { set_error("amp_aa_unit_forward: workspace %zu < %zu bytes", ws_bytes, need); return AMP_ERR_INVALID; }
+    float* s0 = (float*)ws_dev;
+    float* s1 = s0 + (size_t)B * h->C * T;
+    AMP_HIP(launch_act1d(x_dev, s0, B, h->C, T, h->a1, h->ib1, h->filt, h->filt + 12, nullptr, 1, st));
+    AMP_RC(conv_run(h->c1.get(), s0, B, T, 1.f, nullptr, 1.f, s1, 0, 1.f, st));
+    AMP_HIP(launch_act1d(s1, s0, B, h->C, T, h->a2, h->ib2, h->filt, h->filt + 12, nullptr, 1, st));
+    AMP_RC(conv_run(h->c2.get(), s0, B, T, 1.f, x_dev, 1.f, y_dev, 0, 1.f, st));
+    return AMP_OK;
+}
+
+void amp_aa_unit_destroy(amp_aa_unit* h) { delete h; }
 
 int amp_sconv_create(int cin, int cout, int stride, int padding, const float* weight_host, const float* bias_host, amp_sconv** out) {
     if (!weight_host || !out) { set_error("amp_sconv_create: null argument"); return AMP_ERR_INVALID; }

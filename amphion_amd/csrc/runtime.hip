@@ -193,8 +193,9 @@ extern "C" {
 // amp_set_wn_layer_fusion are gone with the kernels behind them (never chosen by the launch policy), amp_set_pair_strips(1) is refused; amp_mel_forward
 // accepts every n_fft in [64, 4096]; 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision / amp_pw_destroy and
 // amp_istft_same_polar, amp_dwconv_layer_norm_c takes K = 7; 144 (additive): the DiffWave entry points amp_dw_* (diffwave.hip); 145 / 146 (additive): the codec entry
-// points (fvq.hip, codec.hip); 147 (additive): amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add, amp_semantic_prepare
-int amp_version(void) { return 147; }
+// points (fvq.hip, codec.hip); 147 (additive): amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add, amp_semantic_prepare;
+// 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip)
+int amp_version(void) { return 148; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

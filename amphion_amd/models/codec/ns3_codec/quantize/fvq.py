@@ -1,0 +1,182 @@
+"""FactorizedVectorQuantize drop-in (models/codec/ns3_codec/quantize/fvq.py:16-116), eval mode, on the exact-fp32 quantizer kernels
+(csrc/fvq.hip).  Same constructor and ``state_dict`` keys: ``in_proj`` / ``out_proj`` are weight-normed ``nn.Linear`` in the reference
+(``bias``, ``weight_g`` [out, 1], ``weight_v`` [out, in]; a folded ``weight`` [out, in] loads too) and are folded exactly as the k = 1 convs of the
+other codecs are, ``_codebook.weight`` [K, d].  The look-up is always L2-normalised (fvq.py:99-101).  Training mode raises
+``NotImplementedError``: the kernels have no backward."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from amphion_amd import _lib
+from amphion_amd._lib import ptr as _p
+from amphion_amd.models.codec.amphion_codec.quantize.factorized_vector_quantize import _no_training
+
+__all__ = ["FactorizedVectorQuantize"]
+
+
+class WNLinear(nn.Module):
+    """The parameters of ``weight_norm(nn.Linear(cin, cout))`` under torch's keys, or of the plain Linear once folded"""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        ref = nn.Linear(cin, cout)
+        self.cin, self.cout = cin, cout
+        self.bias = nn.Parameter(ref.bias.data.clone())
+        self.weight_g = nn.Parameter(ref.weight.data.norm(dim=1, keepdim=True))
+        self.weight_v = nn.Parameter(ref.weight.data.clone())
+
+    @property
+    def has_weight_norm(self):
+        return "weight_g" in self._parameters
+
+    def folded_weight(self):
+        """g * v / ||v|| with the norm over all but dim 0 (torch.nn.utils.weight_norm)"""
+        if not self.has_weight_norm:
+            return self.weight
+        return self.weight_g * (self.weight_v / self.weight_v.norm(dim=1, keepdim=True))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        has_w = prefix + "weight" in state_dict
+        has_gv = prefix + "weight_g" in state_dict and prefix + "weight_v" in state_dict
+        if self.has_weight_norm and has_w and not has_gv:
+            w = self.folded_weight().detach()
+            del self._parameters["weight_g"]
+            del self._parameters["weight_v"]
+            self.weight = nn.Parameter(w)
+        elif not self.has_weight_norm and has_gv and not has_w:
+            w = self._parameters.pop("weight")
+            self.weight_g = nn.Parameter(w.data.norm(dim=1, keepdim=True))
+            self.weight_v = nn.Parameter(w.data.clone())
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+
+class Handle:
+    """The device copy of a stack of levels for ``amp_fvq_*``, rebuilt when a parameter or the device changes"""
+
+    def __init__(self):
+        self._h, self._sig, self._fin = None, None, None
+
+    def __deepcopy__(self, memo):
+        return Handle()
+
+    def get(self, levels, device):
+        sig = tuple((p.data_ptr(), p._version) for q in levels for p in q.parameters()) + (str(device), len(levels))
+        if self._h is not None and sig == self._sig:
+            return self._h
+        if self._fin is not None:
+            self._fin()
+        keep = []
+
+        def host(t):
+            t = t.detach().to("cpu", torch.float32).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        n = len(levels)
+        arr = lambda vals: (ctypes.c_void_p * n)(*vals)     # noqa: E731
+        q0 = levels[0]
+        if any((q.dim, q.codebook_dim, q.codebook_size) != (q0.dim, q0.codebook_dim, q0.codebook_size) for q in levels):
+            raise NotImplementedError("ResidualVQ: levels whose codebook sizes differ are not on the HIP path (one kernel walks all levels)")
+        cb = arr([host(q._codebook.weight) for q in levels])
+        if q0.dim != q0.codebook_dim:
+            wi = arr([host(q.in_proj.folded_weight()) for q in levels])
+            bi = arr([host(q.in_proj.bias) for q in levels])
+            wo = arr([host(q.out_proj.folded_weight()) for q in levels])
+            bo = arr([host(q.out_proj.bias) for q in levels])
+        else:
+            wi = bi = wo = bo = None
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().amp_fvq_create(q0.dim, q0.codebook_dim, q0.codebook_size, n, 1, wi, bi, cb, wo, bo, ctypes.byref(h)))
+        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_fvq_destroy", h)
+        return h
+
+
+def fvq_encode(handle, levels, z, n, sub=None, want_all=True):
+    """z [B, D, T] -> (codes int64 [n, B, T], sum of the levels' z_q (+ sub) [B, D, T], every level's z_q [n, B, D, T] or None).  ``sub``
+    [B, D, T]: the residual starts as z - sub (``amp_fvq_encode_ex``)."""
+    D = levels[0].dim
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] < 1 or z.shape[2] < 1:
+        raise ValueError(f"quantizer: expected a non-empty [B, {D}, T] tensor, got {tuple(z.shape) if isinstance(z, torch.Tensor) else type(z)}")
+    if z.shape[1] != D:
+        raise ValueError(f"quantizer: expected {D} input channels, got {z.shape[1]}")
+    z = _lib.require_device_tensor(z, "quantizer input")
+    B, _, T = z.shape
+    if sub is not None:
+        sub = _lib.require_device_tensor(sub, "subtracted latent")
+        if tuple(sub.shape) != (B, D, T):
+            raise ValueError(f"quantizer: the subtracted latent must be {(B, D, T)}, got {tuple(sub.shape)}")
+    dev = z.device
+    h = handle.get(levels, dev)
+    codes = torch.empty((n, B, T), dtype=torch.int64, device=dev)
+    zq = torch.empty((B, D, T), dtype=torch.float32, device=dev)
+    allq = torch.empty((n, B, D, T), dtype=torch.float32, device=dev) if want_all else None
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().amp_fvq_encode_ex(h, _p(z), T, _p(sub), B, T, n, _p(codes), _p(zq), _p(allq), None, _lib.current_stream_ptr(dev)))
+    return codes, zq, allq
+
+
+def fvq_decode(handle, levels, codes, n, add=None):
+    """codes integers [>= n, B, T] on the device -> sum of the first n levels' out_proj(codebook[code]) (+ add) [B, D, T]; an index outside
+    the codebook raises ``AmpError`` (AMP_ERR_INVALID)"""
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 3 or codes.shape[0] < n or codes.shape[1] < 1 or codes.shape[2] < 1:
+        raise ValueError(f"vq2emb: expected codes [>= {n}, B, T], got {tuple(codes.shape) if isinstance(codes, torch.Tensor) else type(codes)}")
+    if codes.dtype.is_floating_point or codes.dtype == torch.bool:
+        raise TypeError(f"vq2emb: the codes must be integers, got {codes.dtype}")
+    if not codes.is_cuda:
+        raise RuntimeError("vq2emb: the codes must be a tensor on a ROCm device (there is no CPU fallback)")
+    codes = codes[:n].to(torch.int64).contiguous()
+    _, B, T = codes.shape
+    dev = codes.device
+    h = handle.get(levels, dev)
+    out = torch.empty((B, levels[0].dim, T), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        st = _lib.current_stream_ptr(dev)
+        _lib.check(_lib.lib().amp_fvq_decode_add(h, _p(codes), n, B, T, _p(add), _p(out), st))
+        _lib.check(_lib.lib().amp_fvq_check(h, st))
+    return out
+
+
+class FactorizedVectorQuantize(nn.Module):
+    def __init__(self, dim, codebook_size, codebook_dim, commitment, **kwargs):
+        super().__init__()
+        self.dim = dim
+        self.codebook_size = codebook_size
+        self.codebook_dim = codebook_dim
+        self.commitment = commitment
+        if dim != self.codebook_dim:
+            self.in_proj = WNLinear(dim, self.codebook_dim)
+            self.out_proj = WNLinear(self.codebook_dim, dim)
+        else:
+            self.in_proj = nn.Identity()
+            self.out_proj = nn.Identity()
+        self._codebook = nn.Embedding(codebook_size, self.codebook_dim)
+        self._handle = Handle()
+
+    @property
+    def codebook(self):
+        return self._codebook
+
+    def forward(self, z):
+        """z [B, D, T] -> (z_q [B, D, T], indices [B, T], commit_loss [B] = 0)"""
+        _no_training(self, "FactorizedVectorQuantize")
+        codes, z_q, _ = fvq_encode(self._handle, [self], z, 1, want_all=False)
+        return z_q, codes[0], torch.zeros(z.shape[0], device=z.device)
+
+    def vq2emb(self, vq, proj=True):
+        if not proj:
+            return self.embed_code(vq).transpose(1, 2)
+        return fvq_decode(self._handle, [self], vq[None], 1)
+
+    def get_emb(self):
+        return self.codebook.weight
+
+    def embed_code(self, embed_id):
+        return F.embedding(embed_id, self.codebook.weight)
+
+    def decode_code(self, embed_id):
+        return self.embed_code(embed_id).transpose(1, 2)

@@ -1,0 +1,196 @@
+"""The timbre encoder of FACodec (models/codec/ns3_codec/transformer.py:35-234): 4 pre-LN transformer layers (hidden 256, 4 heads, FFN
+Conv1d(256, 1024, 5) -> ReLU -> Linear), eval mode, ``use_cln=False``.  Same class names, constructor arguments and ``state_dict`` keys
+(``nn.LayerNorm`` / ``nn.MultiheadAttention`` / ``nn.Conv1d`` / ``nn.Linear`` hold the parameters; their forwards are not used).
+
+It runs once per utterance at the frame rate and is composed channel-first ([B, 256, T]) from existing launches: the channel LayerNorm
+(``amp_layer_norm_c``), the pointwise GEMM (``amp_pw_forward``) for the q | k | v projection, out_proj and ffn_2 -- the last two with its
+``res + gamma (.) (Wx + b)`` epilogue and gamma = 1, which adds the residual stream AFTER the accumulation -- the conv kernel for the k = 5
+conv with ReLU on store, and torch's scaled-dot-product attention on the device for the attention core.  (The conv kernels' own residual
+argument starts the accumulator from bias + residual, so every product is rounded at the magnitude of the residual stream: measured 2.6 -
+8.3e-6 per ffn_2 on a stream of magnitude 4 - 8, against 0.3 - 0.5e-6 for an fp32 GEMM that adds the stream last.  Fine for a waveform, not
+for an embedding that is compared at 1e-6.)
+
+The position-embedding quirk of the reference is kept: ``PositionalEncoding.forward`` adds ``pe[: x.size(0)]`` to a BATCH-FIRST tensor
+(transformer.py:50, called with [B, T, d]), so row ``pe[b]`` is added to EVERY frame of item b -- the result depends on the item's index in the
+batch, not on time.  ``use_cln=True`` (StyleAdaptiveLayerNorm) is not on the HIP path."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from amphion_amd import _lib
+from amphion_amd._lib import ptr as _p
+from amphion_amd.models.codec.amphion_codec.vocos import _PwHandle, pw_forward
+from amphion_amd.modules.hip_ops import add_channel_bias_, layer_norm_c
+
+AMP_PW_BIAS, AMP_PW_SCALE_RES = 0, 2      # include/amphion_hip.h: amp_pw_epilogue
+
+
+class _LinearView:
+    """what ``_PwHandle`` reads of an nn.Linear, for a weight / bias pair held elsewhere (``MultiheadAttention.in_proj_*``)"""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+        self.out_features, self.in_features = weight.shape
+
+
+def pw(handle, lin, x, res=None):
+    """lin(x) along the channel axis of x [B, cin, T] (+ res, added after the accumulation) -> [B, cout, T]"""
+    out = torch.empty((x.shape[0], lin.out_features, x.shape[2]), dtype=torch.float32, device=x.device)
+    if res is None:
+        return pw_forward(handle, lin, x, AMP_PW_BIAS, out)
+    return pw_forward(handle, lin, x, AMP_PW_SCALE_RES, out, gamma=torch.ones(lin.out_features, dtype=torch.float32, device=x.device), res=res)
+
+
+class ConvCache:
+    """An ``amp_conv`` handle for a Conv1d / Linear whose parameters live in a torch module: weight [cout, cin, k] or [cout, cin], rebuilt when
+    a parameter, the device or the precision changes.  Owns no parameters."""
+
+    def __init__(self, k=1, padding=0, tanh=False):
+        self.k, self.padding, self.tanh = k, padding, tanh
+        self._h = self._fin = self._sig = None
+
+    def __deepcopy__(self, memo):
+        return ConvCache(self.k, self.padding, self.tanh)
+
+    def _ensure(self, weight, bias, device):
+        sig = (weight.data_ptr(), weight._version, None if bias is None else (bias.data_ptr(), bias._version), str(device), _lib.get_precision())
+        if self._h is not None and sig == self._sig:
+            return self._h
+        if self._fin is not None:
+            self._fin()
+        w = weight.detach().to("cpu", torch.float32).contiguous()
+        b = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
+        cout, cin = w.shape[0], w.shape[1]
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().amp_conv_create(0, cin, cout, self.k, 1, 1, self.padding, _p(w), _p(b), ctypes.byref(h)))
+            if self.tanh:
+                _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_TANH, 1))
+        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
+        return h
+
+    def __call__(self, weight, bias, x, slope_out=1.0):
+        """x [B, cin, T] -> lrelu_out(conv(x) + bias) [B, cout, T] (slope_out = 0: ReLU)"""
+        B, _, T = x.shape
+        dev = x.device
+        h = self._ensure(weight, bias, dev)
+        out = torch.empty((B, weight.shape[0], T), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(_lib.lib().amp_conv_forward(h, _p(x), B, T, 1.0, None, float(slope_out), _p(out), _lib.current_stream_ptr(dev)))
+        return out
+
+
+class PositionalEncoding(nn.Module):
+    def __init__(self, d_model, dropout, max_len=5000):
+        super().__init__()
+        self.dropout = dropout
+        position = torch.arange(max_len).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2) * (-math.log(10000.0) / d_model))
+        pe = torch.zeros(max_len, 1, d_model)
+        pe[:, 0, 0::2] = torch.sin(position * div_term)
+        pe[:, 0, 1::2] = torch.cos(position * div_term)
+        self.register_buffer("pe", pe)
+
+    def forward_cf(self, x):
+        """x [B, d, T] channel-first -> a new tensor with pe[b] added to every frame of item b (the reference's quirk, see the module docstring)"""
+        B = x.shape[0]
+        if B > self.pe.shape[0]:
+            raise ValueError(f"PositionalEncoding: batch {B} exceeds the table's {self.pe.shape[0]} rows (the reference indexes it with the batch size)")
+        return add_channel_bias_(x.clone(), self.pe[:B, 0].contiguous())
+
+
+class TransformerFFNLayer(nn.Module):
+    def __init__(self, encoder_hidden, conv_filter_size, conv_kernel_size, encoder_dropout):
+        super().__init__()
+        self.encoder_hidden = encoder_hidden
+        self.conv_filter_size = conv_filter_size
+        self.conv_kernel_size = conv_kernel_size
+        self.encoder_dropout = encoder_dropout
+        if conv_kernel_size % 2 != 1:
+            raise NotImplementedError("TransformerFFNLayer: an even conv_kernel_size changes the length; not on the HIP path")
+        self.ffn_1 = nn.Conv1d(encoder_hidden, conv_filter_size, conv_kernel_size, padding=conv_kernel_size // 2)
+        self.ffn_1.weight.data.normal_(0.0, 0.02)
+        self.ffn_2 = nn.Linear(conv_filter_size, encoder_hidden)
+        self.ffn_2.weight.data.normal_(0.0, 0.02)
+        self._c1, self._c2 = ConvCache(conv_kernel_size, conv_kernel_size // 2), _PwHandle()
+
+    def forward_cf(self, x, res):
+        """res + ffn_2(relu(ffn_1(x))), channel-first"""
+        h = self._c1(self.ffn_1.weight, self.ffn_1.bias, x, slope_out=0.0)
+        return pw(self._c2, self.ffn_2, h, res=res)
+
+
+class TransformerEncoderLayer(nn.Module):
+    def __init__(self, encoder_hidden, encoder_head, conv_filter_size, conv_kernel_size, encoder_dropout, use_cln):
+        super().__init__()
+        if use_cln:
+            raise NotImplementedError("TransformerEncoderLayer: use_cln=True (StyleAdaptiveLayerNorm) is not on the HIP path")
+        self.encoder_hidden = encoder_hidden
+        self.encoder_head = encoder_head
+        self.conv_filter_size = conv_filter_size
+        self.conv_kernel_size = conv_kernel_size
+        self.encoder_dropout = encoder_dropout
+        self.use_cln = use_cln
+        self.ln_1 = nn.LayerNorm(encoder_hidden)
+        self.ln_2 = nn.LayerNorm(encoder_hidden)
+        self.self_attn = nn.MultiheadAttention(encoder_hidden, encoder_head, batch_first=True)
+        self.ffn = TransformerFFNLayer(encoder_hidden, conv_filter_size, conv_kernel_size, encoder_dropout)
+        self._qkv, self._out = _PwHandle(), _PwHandle()
+
+    def forward_cf(self, x):
+        B, H, T = x.shape
+        nh = self.encoder_head
+        a = self.self_attn
+        h = layer_norm_c(x, self.ln_1.weight.detach(), self.ln_1.bias.detach(), eps=self.ln_1.eps)
+        qkv = pw(self._qkv, _LinearView(a.in_proj_weight, a.in_proj_bias), h)
+        q, k, v = (t.reshape(B, nh, H // nh, T).transpose(2, 3) for t in qkv.chunk(3, 1))
+        att = F.scaled_dot_product_attention(q, k, v).transpose(2, 3).reshape(B, H, T).contiguous()
+        x = pw(self._out, a.out_proj, att, res=x)
+        h = layer_norm_c(x, self.ln_2.weight.detach(), self.ln_2.bias.detach(), eps=self.ln_2.eps)
+        return self.ffn.forward_cf(h, x)
+
+
+class TransformerEncoder(nn.Module):
+    def __init__(self, enc_emb_tokens=None, encoder_layer=4, encoder_hidden=256, encoder_head=4, conv_filter_size=1024, conv_kernel_size=5,
+                 encoder_dropout=0.1, use_cln=False, cfg=None):
+        super().__init__()
+        self.encoder_layer = encoder_layer if encoder_layer is not None else cfg.encoder_layer
+        self.encoder_hidden = encoder_hidden if encoder_hidden is not None else cfg.encoder_hidden
+        self.encoder_head = encoder_head if encoder_head is not None else cfg.encoder_head
+        self.conv_filter_size = conv_filter_size if conv_filter_size is not None else cfg.conv_filter_size
+        self.conv_kernel_size = conv_kernel_size if conv_kernel_size is not None else cfg.conv_kernel_size
+        self.encoder_dropout = encoder_dropout if encoder_dropout is not None else cfg.encoder_dropout
+        self.use_cln = use_cln if use_cln is not None else cfg.use_cln
+        if self.use_cln:
+            raise NotImplementedError("TransformerEncoder: use_cln=True (StyleAdaptiveLayerNorm) is not on the HIP path")
+        if enc_emb_tokens is not None:
+            raise NotImplementedError("TransformerEncoder: token embeddings are not on the HIP path (FACodec passes features)")
+        self.use_enc_emb = False
+        self.position_emb = PositionalEncoding(self.encoder_hidden, self.encoder_dropout)
+        self.layers = nn.ModuleList([TransformerEncoderLayer(self.encoder_hidden, self.encoder_head, self.conv_filter_size, self.conv_kernel_size,
+                                                             self.encoder_dropout, self.use_cln) for _ in range(self.encoder_layer)])
+        self.last_ln = nn.LayerNorm(self.encoder_hidden)
+
+    def forward_cf(self, x):
+        """x [B, hidden, T] channel-first -> [B, hidden, T]"""
+        if self.training:
+            raise NotImplementedError("TransformerEncoder: training mode (dropout) is not on the HIP path: call .eval()")
+        x = _lib.require_device_tensor(x, "TransformerEncoder input")
+        if x.dim() != 3 or x.shape[1] != self.encoder_hidden or x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"TransformerEncoder: expected a non-empty [B, {self.encoder_hidden}, T] input, got {tuple(x.shape)}")
+        with _lib.on_device(x.device):
+            x = self.position_emb.forward_cf(x)
+            for layer in self.layers:
+                x = layer.forward_cf(x)
+            return layer_norm_c(x, self.last_ln.weight.detach(), self.last_ln.bias.detach(), eps=self.last_ln.eps)
+
+    def forward(self, x, key_padding_mask=None, condition=None):
+        """x [B, T, hidden] batch-first, as the reference takes it -> [B, T, hidden]"""
+        if key_padding_mask is not None or condition is not None:
+            raise NotImplementedError("TransformerEncoder: a padding mask / condition is not on the HIP path (FACodec passes None)")
+        return self.forward_cf(x.transpose(1, 2).contiguous()).transpose(1, 2)

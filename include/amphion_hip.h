@@ -96,7 +96,8 @@ typedef struct amp_gen amp_gen;
  * amp_pw_destroy and amp_istft_same_polar, and amp_dwconv_layer_norm_c accepts K = 7 (C <= 1024); 144 (additive): the DiffWave entry
  * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*;
  * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
- * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare. */
+ * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
+ * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -747,6 +748,28 @@ size_t amp_tconv_workspace_bytes(const amp_tconv* h, int B, int T);
 int amp_tconv_forward(const amp_tconv* h, const float* x_dev, int B, int T, const float* alpha_dev, void* ws_dev, size_t ws_bytes, float* y_dev,
                       void* stream);
 void amp_tconv_destroy(amp_tconv* h);
+
+/* ResidualUnit of FACodec (models/codec/ns3_codec/facodec.py): y = x + conv1x1(A2(conv7(A1(x)))) with A = Activation1d(Snake | SnakeBeta),
+ * BigVGAN's anti-aliased activation (2x up-sampling FIR -> Snake -> 2x down-sampling FIR, 12 taps each, replicate padding at the item's
+ * ends: amp_antialias_snake), conv7 = Conv1d(C, C, 7, dilation, padding 3 * dilation).  alpha*_host / beta*_host [C] as stored (beta NULL = plain
+ * Snake; logscale != 0: both are exponents), w1_host [C, C, 7] and w2_host [C, C, 1] FOLDED, biases [C], filt_up12 / filt_down12 the two 12-tap
+ * filters.  The fused launch (csrc/aa_unit_f16x3.hip) is built for AMP_PRECISION_F16X3 with C % 32 == 0, C <= 128 and dilation <= 9 and needs
+ * no workspace; amp_aa_unit_fused tells which route a handle took.  Otherwise -- other widths, and every unit under AMP_PRECISION_F32 -- the
+ * handle runs act1d -> conv -> act1d -> conv (+ residual) on the existing kernels, bit for bit amp_antialias_snake / amp_conv_forward /
+ * amp_antialias_snake / amp_conv_forward_mrf(res = x), with a workspace of amp_aa_unit_workspace_bytes (two [B, C, T] tensors).  The f16x3 forms
+ * feed the op-level range flag (amp_range_check).  Fused limits: T <= 2^29 and B * ceil(T / 54) < 2^31, else AMP_ERR_UNSUPPORTED.
+ * y_dev must not alias x_dev.  No allocation, no synchronisation in forward; deterministic; an item never depends on its batch. */
+typedef struct amp_aa_unit amp_aa_unit;
+int amp_aa_unit_create(int channels, int dilation, const float* alpha1_host, const float* beta1_host, const float* w1_host, const float* b1_host,
+                       const float* alpha2_host, const float* beta2_host, const float* w2_host, const float* b2_host, int logscale,
+                       const float* filt_up12_host, const float* filt_down12_host, amp_aa_unit** out);
+int amp_aa_unit_fused(const amp_aa_unit* h);
+/* Which route handles created AFTER the call take: -1 (default) the measured policy, 0 the four launches everywhere, 1 the
+ * fused launch wherever it is built -- an A/B switch for tools/facodec_bench.py and the tests. */
+int amp_set_aa_unit_fusion(int mode);
+size_t amp_aa_unit_workspace_bytes(const amp_aa_unit* h, int B, int T);
+int amp_aa_unit_forward(const amp_aa_unit* h, const float* x_dev, int B, int T, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream);
+void amp_aa_unit_destroy(amp_aa_unit* h);
 
 #ifdef __cplusplus
 }
