@@ -530,6 +530,8 @@ hipError_t launch_snake(const float* x, float* y, int B, int C, int T, const flo
                         int logscale, hipStream_t stream) {
     const size_t blocks = (size_t)B * C * ((T + 1023) / 1024);
     if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    note_kernel("snake_kernel");
+    note_work(blocks, 0.0, 2 * 4.0 * B * (double)C * T / 1e6, "Snake C=%d T=%d B=%d", C, T, B);
     hipLaunchKernelGGL(snake_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, y, alpha, beta, logscale, C, T);
     return hipGetLastError();
 }

@@ -226,3 +226,48 @@ def margin_rule(sd, hp, z, n=None, prefix="quantizers."):
     tau = 8.0 * max(float((a.double() - b).abs().max()) for a, b in zip(r32["dist"], r64["dist"]))
     decided = torch.cumprod((r64["margin"] > tau).to(torch.int64), dim=0).bool()
     return r64, r32, tau, decided
+
+
+# ---- the derived bounds of the f16x3 ops (tests/test_gpu_codec.py states the derivation) ---------------------------------------------
+def d_snake(v, a):
+    """error of the library's snake on an exact fp32 argument: (3.3e-7 + 1.2e-7 |a v|) / a + 2.4e-7 |snake(v)|"""
+    return (3.3e-7 + 1.2e-7 * (a * v).abs()) / a + 2.4e-7 * snake(v, a).abs()
+
+
+def sconv_bound(w, b, alpha, x, stride, padding):
+    """fp64 output of [snake ->] Conv1d(k = 2 stride, stride, padding) and the derived bound of each element:
+    2e-6 (|w| * |snake(x)| + |b|) + 3e-7 |ref| + |w| * d_snake(x)"""
+    kw = dict(stride=stride, padding=padding)
+    s1 = x if alpha is None else snake(x, alpha)
+    ref = Fn.conv1d(s1, w, b, **kw)
+    tol = 2e-6 * (Fn.conv1d(s1.abs(), w.abs(), **kw) + b.abs()[None, :, None]) + 3e-7 * ref.abs()
+    if alpha is not None:
+        tol = tol + Fn.conv1d(d_snake(x, alpha), w.abs(), **kw)
+    return ref, tol
+
+
+def unit_bound(sd64, x, dil, padding=None):
+    """fp64 output of the residual unit and the derived bound of each element; padding: conv7's, 3 * dil (the unit's own) when None"""
+    pad = 3 * dil if padding is None else padding
+    a1, a2 = sd64["0.alpha"], sd64["2.alpha"]
+    w1, w2 = folded(sd64, "1."), folded(sd64, "3.")
+    b1, b2 = sd64["1.bias"], sd64["3.bias"]
+    s1 = snake(x, a1)
+    v = Fn.conv1d(s1, w1, b1, dilation=dil, padding=pad)
+    tol1 = 2e-6 * (Fn.conv1d(s1.abs(), w1.abs(), dilation=dil, padding=pad) + b1.abs()[None, :, None]) + 3e-7 * v.abs() \
+        + Fn.conv1d(d_snake(x, a1), w1.abs(), dilation=dil, padding=pad)
+    z = snake(v, a2)
+    dz = 2 * tol1 + d_snake(v, a2)
+    r = Fn.conv1d(z, w2, b2)
+    tol2 = Fn.conv1d(dz, w2.abs()) + 2e-6 * (Fn.conv1d(z.abs(), w2.abs()) + b2.abs()[None, :, None]) + 3e-7 * r.abs()
+    y = x + r
+    return y, tol2 + 1.2e-7 * (x.abs() + r.abs()) + 1.2e-7 * y.abs()
+
+
+def unit_param_shapes(Cn):
+    """the residual unit's own state_dict: 0.alpha, 1. (conv7), 2.alpha, 3. (conv 1 x 1)"""
+    shapes = {"0.alpha": (1, Cn, 1)}
+    _wn(shapes, "1.", Cn, Cn, 7)
+    shapes["2.alpha"] = (1, Cn, 1)
+    _wn(shapes, "3.", Cn, Cn, 1)
+    return shapes

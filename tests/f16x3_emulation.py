@@ -37,8 +37,10 @@ def split(v):
     return hi, (v - hi).half().float()
 
 
-def conv(x, w, b=None, *, transposed=False, stride=1, dilation=1, padding=0, slope_in=1.0, res=None, slope_out=1.0, terms=3):
-    """y = lrelu(conv(lrelu(x, slope_in), w) + b + res, slope_out) in the kernels' split-f16 arithmetic (fp32 in and out)"""
+def conv(x, w, b=None, *, transposed=False, stride=1, dilation=1, padding=0, slope_in=1.0, res=None, slope_out=1.0, terms=3,
+         output_padding=0):
+    """y = lrelu(conv(lrelu(x, slope_in), w) + b + res, slope_out) in the kernels' split-f16 arithmetic (fp32 in and out);
+    output_padding: ConvTranspose1d's (transposed only)"""
     xl = x.float() * XS
     if slope_in != 1.0:
         xl = torch.maximum(xl, xl * slope_in)
@@ -46,7 +48,7 @@ def conv(x, w, b=None, *, transposed=False, stride=1, dilation=1, padding=0, slo
     xh, xlo = split(xl)
     wh, wlo = split(w.float() * S)
     if transposed:
-        op = lambda a, ww: _conv_transpose1d(a, ww, stride=stride, padding=padding)
+        op = lambda a, ww: _conv_transpose1d(a, ww, stride=stride, padding=padding, output_padding=output_padding)
     else:
         op = lambda a, ww: _conv1d(a, ww, dilation=dilation, padding=padding)
     acc = op(xh, wh)

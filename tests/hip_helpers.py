@@ -164,3 +164,188 @@ def ampblock_forward(ws1, bs1, ws2, bs2, alphas, betas, logscale, fu, fd, x, *, 
     finally:
         for h in h1 + h2:
             L.amp_conv_destroy(h)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the codec ops (amp_tconv_*, amp_sconv_*, amp_codec_unit_*, amp_aa_unit_*): CPU tensors in and out, like conv_forward.  Every output and
+# workspace lies inside a larger NaN-filled buffer with SENTINEL floats in front and behind: after the call the sentinels must be untouched
+# and every output element finite (a dropped store is a NaN).  `xs` may be one tensor or a list of them (one handle, one call each; a list
+# comes back).  `info`, when given, receives the handle's route ("fused") and the library's output lengths ("out_len": {T: T_out}).
+# ------------------------------------------------------------------------------------------------------------------------------
+SENTINEL = 64
+_NAN_BITS = int(torch.full((1,), float("nan")).view(torch.int32).item())
+
+
+class Guarded:
+    """a NaN-filled device tensor of `shape` between two runs of SENTINEL NaN floats; 16-byte aligned"""
+
+    def __init__(self, shape):
+        self.n = 1
+        for v in shape:
+            self.n *= int(v)
+        self.buf = torch.full((self.n + 2 * SENTINEL,), float("nan"), device="cuda")
+        self.t = self.buf[SENTINEL:SENTINEL + self.n].view(*shape)
+        assert self.t.data_ptr() % 16 == 0
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.t.data_ptr())
+
+    def check(self, what, finite=True):
+        bits = self.buf.view(torch.int32)
+        for name, part in (("in front of", bits[:SENTINEL]), ("behind", bits[SENTINEL + self.n:])):
+            hit = (part != _NAN_BITS).nonzero().flatten().tolist()
+            assert not hit, f"{what}: the sentinel floats {hit[:8]} {name} the tensor were written"
+        if finite:
+            bad = (~torch.isfinite(self.t)).nonzero()
+            assert bad.numel() == 0, (f"{what}: {bad.shape[0]} of {self.n} outputs were not written or are not finite; first at "
+                                      f"{bad[:6].tolist()} of {tuple(self.t.shape)}")
+
+
+def _cp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _host(t):
+    return t.detach().contiguous().float().cpu() if t is not None else None
+
+
+def _as_list(xs):
+    return (list(xs), True) if isinstance(xs, (list, tuple)) else ([xs], False)
+
+
+class _Fusion:
+    """amp_set_*_fusion(mode) around a create; back to the policy afterwards"""
+
+    def __init__(self, setter, mode):
+        self.setter, self.mode = setter, mode
+
+    def __enter__(self):
+        if self.mode is not None:
+            _lib.check(self.setter(int(self.mode)))
+
+    def __exit__(self, *exc):
+        if self.mode is not None:
+            _lib.check(self.setter(-1))
+
+
+def tconv_forward(w, b, xs, alpha=None, *, stride, padding, output_padding=0, fusion=None, info=None):
+    """amp_tconv_*: y = ConvTranspose1d(k = 2 stride, stride, padding, output_padding)([snake](x)).  w [cin, cout, 2 stride] folded, b [cout] or
+    None, alpha [cin] or None; fusion: amp_set_tconv_fusion's mode for this handle."""
+    L = _lib.lib()
+    w, b, alpha = _host(w), _host(b), _host(alpha)
+    cin, cout, k = w.shape
+    assert k == 2 * stride
+    xs, many = _as_list(xs)
+    h = ctypes.c_void_p()
+    with _Fusion(L.amp_set_tconv_fusion, fusion):
+        _lib.check(L.amp_tconv_create(cin, cout, stride, padding, output_padding, _cp(w), _cp(b), ctypes.byref(h)))
+    try:
+        if info is not None:
+            info.update(fused=int(L.amp_tconv_fused(h)), out_len={})
+        ad = alpha.reshape(-1).cuda() if alpha is not None else None
+        out = []
+        for x in xs:
+            xd = _host(x).cuda()
+            B, _, T = xd.shape
+            Tout = L.amp_tconv_out_len(h, T)
+            if info is not None:
+                info["out_len"][T] = Tout
+            y = Guarded((B, cout, Tout if Tout > 0 else 1))       # (T_out <= 0 is the library's to refuse: it still gets a real pointer)
+            need = L.amp_tconv_workspace_bytes(h, B, T)
+            ws = Guarded(((need + 3) // 4,)) if need else None
+            _lib.check(L.amp_tconv_forward(h, _cp(xd), B, T, _cp(ad), ws.ptr if ws else None, need, y.ptr, _lib.current_stream_ptr(xd.device)))
+            torch.cuda.synchronize()
+            y.check(f"amp_tconv_forward B={B} T={T}")
+            if ws:
+                ws.check(f"amp_tconv_forward workspace B={B} T={T}", finite=False)
+            out.append(y.t.cpu())
+        return out if many else out[0]
+    finally:
+        L.amp_tconv_destroy(h)
+
+
+def sconv_forward(w, b, xs, alpha=None, *, stride, padding, info=None):
+    """amp_sconv_*: y = Conv1d(k = 2 stride, stride, padding)([snake](x)).  w [cout, cin, 2 stride] folded, b [cout] or None, alpha [cin] or None"""
+    L = _lib.lib()
+    w, b, alpha = _host(w), _host(b), _host(alpha)
+    cout, cin, k = w.shape
+    assert k == 2 * stride
+    xs, many = _as_list(xs)
+    h = ctypes.c_void_p()
+    _lib.check(L.amp_sconv_create(cin, cout, stride, padding, _cp(w), _cp(b), ctypes.byref(h)))
+    try:
+        if info is not None:
+            info.update(out_len={})
+        ad = alpha.reshape(-1).cuda() if alpha is not None else None
+        out = []
+        for x in xs:
+            xd = _host(x).cuda()
+            B, _, T = xd.shape
+            Tout = L.amp_sconv_out_len(h, T)
+            if info is not None:
+                info["out_len"][T] = Tout
+            y = Guarded((B, cout, Tout if Tout > 0 else 1))
+            need = L.amp_sconv_workspace_bytes(h, B, T)
+            ws = Guarded((max(1, (need + 3) // 4),))
+            _lib.check(L.amp_sconv_forward(h, _cp(xd), B, T, _cp(ad), ws.ptr, need, y.ptr, _lib.current_stream_ptr(xd.device)))
+            torch.cuda.synchronize()
+            y.check(f"amp_sconv_forward B={B} T={T}")
+            ws.check(f"amp_sconv_forward workspace B={B} T={T}", finite=need > 0)     # the repack kernel writes every workspace element
+            out.append(y.t.cpu())
+        return out if many else out[0]
+    finally:
+        L.amp_sconv_destroy(h)
+
+
+def _unit_calls(L, h, prefix, xs, C, info):
+    fwd, wsb = getattr(L, prefix + "_forward"), getattr(L, prefix + "_workspace_bytes")
+    if info is not None:
+        info.update(fused=int(getattr(L, prefix + "_fused")(h)))
+    out = []
+    for x in xs:
+        xd = _host(x).cuda()
+        B, _, T = xd.shape
+        y = Guarded((B, C, T))
+        need = wsb(h, B, T)
+        ws = Guarded(((need + 3) // 4,)) if need else None
+        _lib.check(fwd(h, _cp(xd), B, T, y.ptr, ws.ptr if ws else None, need, _lib.current_stream_ptr(xd.device)))
+        torch.cuda.synchronize()
+        y.check(f"{prefix}_forward B={B} T={T}")
+        if ws:
+            ws.check(f"{prefix}_forward workspace B={B} T={T}")
+        out.append(y.t.cpu())
+    return out
+
+
+def codec_unit_forward(alpha1, w1, b1, alpha2, w2, b2, xs, *, dilation, fusion=None, info=None):
+    """amp_codec_unit_*: y = x + conv1x1(snake_2(conv7(snake_1(x)))).  alpha* [C], w1 [C, C, 7] and w2 [C, C, 1] folded, b* [C]"""
+    L = _lib.lib()
+    t = [_host(v) for v in (alpha1, w1, b1, alpha2, w2, b2)]
+    C = t[1].shape[0]
+    xs, many = _as_list(xs)
+    h = ctypes.c_void_p()
+    with _Fusion(L.amp_set_codec_unit_fusion, fusion):
+        _lib.check(L.amp_codec_unit_create(C, dilation, *[_cp(v) for v in t], ctypes.byref(h)))
+    try:
+        out = _unit_calls(L, h, "amp_codec_unit", xs, C, info)
+        return out if many else out[0]
+    finally:
+        L.amp_codec_unit_destroy(h)
+
+
+def aa_unit_forward(alpha1, beta1, w1, b1, alpha2, beta2, w2, b2, fu, fd, xs, *, dilation, logscale=True, fusion=None, info=None):
+    """amp_aa_unit_*: y = x + conv1x1(A2(conv7(A1(x)))), A = Activation1d(SnakeBeta | Snake: beta* None).  fu / fd: the two 12-tap filters"""
+    L = _lib.lib()
+    t = [_host(v) for v in (alpha1, beta1, w1, b1, alpha2, beta2, w2, b2)]
+    f = [_host(fu).reshape(-1), _host(fd).reshape(-1)]
+    C = t[2].shape[0]
+    xs, many = _as_list(xs)
+    h = ctypes.c_void_p()
+    with _Fusion(L.amp_set_aa_unit_fusion, fusion):
+        _lib.check(L.amp_aa_unit_create(C, dilation, *[_cp(v) for v in t], int(logscale), _cp(f[0]), _cp(f[1]), ctypes.byref(h)))
+    try:
+        out = _unit_calls(L, h, "amp_aa_unit", xs, C, info)
+        return out if many else out[0]
+    finally:
+        L.amp_aa_unit_destroy(h)

@@ -172,25 +172,7 @@ def unit_state_dict(Cn, seed):
     return C._synth(shapes, seed)
 
 
-def d_snake(v, a):
-    return (3.3e-7 + 1.2e-7 * (a * v).abs()) / a + 2.4e-7 * C.snake(v, a).abs()
-
-
-def unit_bound(sd64, x, dil):
-    """fp64 output of the unit and the derived bound of each element"""
-    a1, a2 = sd64["0.alpha"], sd64["2.alpha"]
-    w1, w2 = C.folded(sd64, "1."), C.folded(sd64, "3.")
-    b1, b2 = sd64["1.bias"], sd64["3.bias"]
-    s1 = C.snake(x, a1)
-    v = F.conv1d(s1, w1, b1, dilation=dil, padding=3 * dil)
-    tol1 = 2e-6 * (F.conv1d(s1.abs(), w1.abs(), dilation=dil, padding=3 * dil) + b1.abs()[None, :, None]) + 3e-7 * v.abs() \
-        + F.conv1d(d_snake(x, a1), w1.abs(), dilation=dil, padding=3 * dil)
-    z = C.snake(v, a2)
-    dz = 2 * tol1 + d_snake(v, a2)
-    r = F.conv1d(z, w2, b2)
-    tol2 = F.conv1d(dz, w2.abs()) + 2e-6 * (F.conv1d(z.abs(), w2.abs()) + b2.abs()[None, :, None]) + 3e-7 * r.abs()
-    y = x + r
-    return y, tol2 + 1.2e-7 * (x.abs() + r.abs()) + 1.2e-7 * y.abs()
+d_snake, unit_bound = C.d_snake, C.unit_bound          # the derived bounds live next to the fp64 restatement (tests/codec_ref.py)
 
 
 def make_unit(Cn, dil, sd):
@@ -284,15 +266,15 @@ def test_strided_conv_vs_fp64(conv_precision, s):
         ref = C.strided_conv(sd64, "a.alpha", "c.", x64, s)
         assert y.shape == ref.shape and ref.shape[2] == (T + 2 * ((s + 1) // 2) - 2 * s) // s + 1
         p = (s + 1) // 2
-        s1 = C.snake(x64, sd64["a.alpha"])
-        tol = 2e-6 * (F.conv1d(s1.abs(), w.abs(), stride=s, padding=p) + sd64["c.bias"].abs()[None, :, None]) + 3e-7 * ref.abs() \
-            + F.conv1d(d_snake(x64, sd64["a.alpha"]), w.abs(), stride=s, padding=p)
+        ref_b, tol = C.sconv_bound(w, sd64["c.bias"], sd64["a.alpha"], x64, s, p)
+        assert torch.equal(ref_b, ref)
         frac = float(((y - ref).abs() / tol).max())
         worst = max(worst, frac)
         assert frac <= 1.0, (s, T, frac)
         plain = conv(x.to(DEV)).cpu().double()                 # without the activation
         ref0 = C.strided_conv(sd64, None, "c.", x64, s)
-        tol0 = 2e-6 * (F.conv1d(x64.abs(), w.abs(), stride=s, padding=p) + sd64["c.bias"].abs()[None, :, None]) + 3e-7 * ref0.abs()
+        ref0_b, tol0 = C.sconv_bound(w, sd64["c.bias"], None, x64, s, p)
+        assert torch.equal(ref0_b, ref0)
         assert bool(((plain - ref0).abs() <= tol0).all()), (s, T)
     print(f"strided conv s={s} [{conv_precision}]: worst error / bound = {worst:.3f}")
 

@@ -202,14 +202,16 @@ def _child(group, precision, out, cases_fn=None):
 # ------------------------------------------------------------------------------------------------------------------------------
 # parent side: ONE test per (group, precision), so that each child process starts exactly once whatever the number of workers
 # ------------------------------------------------------------------------------------------------------------------------------
-def _run_group(group, precision, tmp_path, cases_fn=None, script=None, title="recipe shapes"):
+def _run_group(group, precision, tmp_path, cases_fn=None, script=None, title="recipe shapes", bound=None):
+    """bound: what a case's figure is printed against (default: the conv bound, ACT_BOUND for act1d); 1 for cases that return error / bound"""
     out, man = tmp_path / "results.json", tmp_path / "manifest.tsv"
     env = dict(os.environ, AMP_LAUNCH_MANIFEST=str(man), AMP_PRECISION=precision)
     r = subprocess.run([sys.executable, os.path.abspath(script or __file__), group, precision, str(out)], capture_output=True, text=True,
                        env=env, timeout=900)
     res = json.load(open(out)) if out.exists() else {}
     problems, table = [], []
-    bound = ACT_BOUND if group == "act1d" else BOUND
+    if bound is None:
+        bound = ACT_BOUND if group == "act1d" else BOUND
     for name, _, kernels in (cases_fn or group_cases)(group, precision):
         if name not in res:
             problems.append(f"{name}: not run (the child ended first)")
