@@ -284,7 +284,6 @@ int amp_fvq_create(int input_dim, int codebook_dim, int codebook_size, int num_q
                    const float* const* in_w_host, const float* const* in_b_host, const float* const* codebook_host,
                    const float* const* out_w_host, const float* const* out_b_host, amp_fvq** out) {
     if (!codebook_host || !out) { set_error("amp_fvq_create: null argument"); return AMP_ERR_INVALID; }
-    if (amp_device_count() <= 0) { set_error("amp_fvq_create: no HIP device visible (the HIP path has no CPU fallback)"); return AMP_ERR_HIP; }
     const int D = input_dim, d = codebook_dim, K = codebook_size, N = num_quantizers;
     if (D < 1 || d < 1 || K < 1 || N < 1) { set_error("amp_fvq_create: D=%d d=%d K=%d N=%d", D, d, K, N); return AMP_ERR_INVALID; }
     if (D > 1024 || d > 32 || K > 16384 || N > 32) {
@@ -336,6 +335,8 @@ int amp_fvq_create(int input_dim, int codebook_dim, int codebook_size, int num_q
             memcpy(&bo[(size_t)l * D], out_b_host[l], sizeof(float) * D);
         }
     }
+    // every refusal above is the host's alone: the arguments are judged the same with or without a device
+    if (amp_device_count() <= 0) { set_error("amp_fvq_create: no HIP device visible (the HIP path has no CPU fallback)"); return AMP_ERR_HIP; }
     AMP_RC(h->dev.upload(cb, &h->cb));
     AMP_RC(h->dev.upload(cbn, &h->cbn));
     AMP_RC(h->dev.upload(cn2, &h->cn2));

@@ -652,7 +652,8 @@ void amp_dw_destroy(amp_dw* h);
 /* Residual factorized VQ in eval mode (csrc/fvq.hip; quantize/residual_vq.py:68-152, factorized_vector_quantize.py:52-127), exact fp32.
  * amp_fvq_create: per level l < num_quantizers the FOLDED in_project [d, D] + bias [d], codebook [K, d], FOLDED out_project [D, d] + bias [D],
  *   as arrays of num_quantizers host pointers; the four projection arrays are all NULL when input_dim == codebook_dim (nn.Identity).
- *   Covered: D <= 1024, d <= 32, K <= 16384, N <= 32; anything else AMP_ERR_UNSUPPORTED.
+ *   Covered: D <= 1024, d <= 32, K <= 16384, N <= 32; anything else AMP_ERR_UNSUPPORTED.  The arguments are judged on the host, before a
+ *   device is asked for: a refusal reads the same with or without one.
  * amp_fvq_encode = ResidualVQ.forward: z [B, D, T] -> codes int64 [n_quantizers, B, T] and (zq_dev not NULL) quantized_out [B, D, T], the sum
  *   of the levels' z_q, and (all_zq_dev not NULL) every level's z_q [n_quantizers, B, D, T] (all_quantized); ONE launch for all levels, the residual stays on chip.  Equal distances resolve to the LOWEST index, as
  *   (-dist).max(1)[1] does.  The distance keeps the reference's expression and order, (sum e^2 - 2 e.c) + sum c^2 on normalised operands.
