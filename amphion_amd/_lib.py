@@ -175,6 +175,19 @@ _SIGNATURES = {
     "amp_tconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "amp_tconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "amp_tconv_destroy": (None, [c_void_p]),
+    "amp_elu_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "amp_lstm_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                POINTER(c_void_p)]),
+    "amp_lstm_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_lstm_out_channels": (c_int, [c_void_p]),
+    "amp_lstm_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_lstm_recur": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_lstm_destroy": (None, [c_void_p]),
+    "amp_evq_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p), POINTER(c_void_p)]),
+    "amp_evq_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_evq_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "amp_evq_check": (c_int, [c_void_p, c_void_p]),
+    "amp_evq_destroy": (None, [c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),

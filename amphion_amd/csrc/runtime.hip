@@ -194,8 +194,9 @@ extern "C" {
 // accepts every n_fft in [64, 4096]; 143 (additive): the Vocos entry points amp_pw_create / amp_pw_forward / amp_pw_precision / amp_pw_destroy and
 // amp_istft_same_polar, amp_dwconv_layer_norm_c takes K = 7; 144 (additive): the DiffWave entry points amp_dw_* (diffwave.hip); 145 / 146 (additive): the codec entry
 // points (fvq.hip, codec.hip); 147 (additive): amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add, amp_semantic_prepare;
-// 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip)
-int amp_version(void) { return 148; }
+// 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip);
+// 149 (additive): SpeechTokenizer's amp_elu_pad (seanet.hip), amp_lstm_* (lstm.hip) and amp_evq_* (evq.hip)
+int amp_version(void) { return 149; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

@@ -97,7 +97,7 @@ typedef struct amp_gen amp_gen;
  * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*;
  * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
  * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
- * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion. */
+ * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -771,6 +771,58 @@ int amp_set_aa_unit_fusion(int mode);
 size_t amp_aa_unit_workspace_bytes(const amp_aa_unit* h, int B, int T);
 int amp_aa_unit_forward(const amp_aa_unit* h, const float* x_dev, int B, int T, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream);
 void amp_aa_unit_destroy(amp_aa_unit* h);
+
+/* ---- SpeechTokenizer (models/codec/speechtokenizer/): SEANet stacks, LSTM, Euclidean residual VQ ---- */
+
+/* The staging pass in front of every SEANet conv (csrc/seanet.hip; modules/conv.py:97-119): y[b, c, j] = act(x[b, c, src(j)]) for
+ * j in [0, pad_left + T + pad_right).  act is ELU (v > 0 ? v : alpha * expm1(v)) when `elu` != 0, else the identity.  src is
+ * F.pad(mode = "reflect") with pad1d's small-input rule: when T <= max(pad_left, pad_right) the row is first zero-extended on the right to
+ * max_pad + 1 samples, then reflected, and the extension is cropped again.  With zero pads it is the element-wise ELU (y may then alias x).
+ * x and y may have any 4-byte alignment (the 16-byte accesses are taken where the addresses allow).  The convs themselves stay on amp_conv_* / amp_sconv_* / amp_tconv_*, fed the padded tensor with padding = 0.  Exact fp32, one pass.
+ * pad_* < 0, B / C / T <= 0 or NULL pointers: AMP_ERR_INVALID; T_out > 2^30 or more than 2^31 - 1 workgroups: AMP_ERR_UNSUPPORTED.  The
+ * arguments are judged on the host alone: no device is asked for before the launch. */
+int amp_elu_pad(const float* x_dev, int B, int C, int T, int pad_left, int pad_right, int elu, float alpha, float* y_dev, void* stream);
+
+/* nn.LSTM in eval mode inside SLSTM (csrc/lstm.hip; modules/lstm.py:18-46), in the conv layout on both sides: x [B, input_size, T] ->
+ * y [B, ndir * hidden, T], ndir = 2 when bidirectional (forward half first, as nn.LSTM concatenates).  Zero initial state, gate order i, f, g, o.
+ * amp_lstm_create: the four arrays hold num_layers * ndir HOST pointers in nn.LSTM's own order (l0, l0_reverse, l1, ..): weight_ih
+ *   [4 hidden, input_size] (layers >= 1: [4 hidden, ndir * hidden]), weight_hh [4 hidden, hidden], bias_ih / bias_hh [4 hidden].  skip != 0 folds
+ *   SLSTM's y + x (x repeated over both halves when bidirectional) into the last layer's store and needs input_size == hidden (else
+ *   AMP_ERR_INVALID).  Covered: hidden <= 1024, input_size <= 2048, num_layers <= 4; anything else AMP_ERR_UNSUPPORTED.  The arguments are judged
+ *   on the host before a device is asked for.
+ * amp_lstm_forward: per layer ONE pointwise GEMM Gx = W_ih x + (b_ih + b_hh) for all T and both directions (the arithmetic the handle was created
+ *   under: f16x3, which feeds the op-level range flag, or exact fp32 under AMP_PRECISION_F32), then the recurrence.
+ * amp_lstm_recur: the recurrence of one layer alone, exact fp32: gx [B, ndir * 4 hidden, T] (per direction the rows of i, f, g, o) ->
+ *   y [B, ndir * hidden, T]; skip_dev [B, hidden, T] or NULL is added at the store.  One launch per time step, enqueued back to back on `stream`;
+ *   both directions share a grid.  ws_dev: at least amp_lstm_workspace_bytes(h, B, T) bytes, 16-byte aligned (else AMP_ERR_INVALID; the state lives at its start).
+ * No allocation and no synchronisation in forward / recur; deterministic; an item's bits do not depend on what it is batched with.
+ * y must not alias x. */
+typedef struct amp_lstm amp_lstm;
+int amp_lstm_create(int input_size, int hidden, int num_layers, int bidirectional, int skip, const float* const* w_ih_host,
+                    const float* const* w_hh_host, const float* const* b_ih_host, const float* const* b_hh_host, amp_lstm** out);
+size_t amp_lstm_workspace_bytes(const amp_lstm* h, int B, int T);
+int amp_lstm_out_channels(const amp_lstm* h);
+int amp_lstm_forward(const amp_lstm* h, const float* x_dev, int B, int T, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int amp_lstm_recur(const amp_lstm* h, int layer, const float* gx_dev, int B, int T, const float* skip_dev, float* y_dev, void* ws_dev, void* stream);
+void amp_lstm_destroy(amp_lstm* h);
+
+/* Residual VQ over full-width Euclidean codebooks in eval mode (csrc/evq.hip; modules/quantization/core_vq.py:180-236,331-388), exact fp32.
+ * amp_evq_create: codebooks[l] [K, D] (EuclideanCodebook.embed) as num_quantizers host pointers.  Covered: D <= 1024, K <= 4096, N <= 32; anything
+ *   else AMP_ERR_UNSUPPORTED; judged on the host before a device is asked for.
+ * amp_evq_encode: z [B, D, T] -> codes int64 [n_q - st, B, T] of levels [st, n_q), and (not NULL) zq [B, D, T] = the sum of those levels' rows,
+ *   all_zq [n_q - st, B, D, T] = every level's rows; ONE launch for all levels, the residual stays on chip.  The distance keeps the reference's
+ *   expression and order, -((sum x^2 - (2 x) . e) + sum e^2); equal distances resolve to the LOWEST index.  With st > 0 level st starts from the
+ *   WHOLE input, as ResidualVectorQuantization.encode does.  0 <= st < n_q <= N, else AMP_ERR_INVALID.
+ * amp_evq_decode: codes [n, B, T] of levels [st, st + n) -> out [B, D, T] = 0 + embed[st][codes[0]] + embed[st + 1][codes[1]] + ..  An index
+ *   outside [0, K) reads row 0 instead (never out of bounds) and sets a device flag of the handle; amp_evq_check works as amp_fvq_check does.
+ * No allocation and no synchronisation in encode / decode; deterministic; a frame never depends on what it is batched with. */
+typedef struct amp_evq amp_evq;
+int amp_evq_create(int dim, int codebook_size, int num_quantizers, const float* const* codebook_host, amp_evq** out);
+int amp_evq_encode(const amp_evq* h, const float* z_dev, int B, int T, int st, int n_q, long long* codes_dev, float* zq_dev, float* all_zq_dev,
+                   void* stream);
+int amp_evq_decode(const amp_evq* h, const long long* codes_dev, int n, int st, int B, int T, float* out_dev, void* stream);
+int amp_evq_check(amp_evq* h, void* stream);
+void amp_evq_destroy(amp_evq* h);
 
 #ifdef __cplusplus
 }
