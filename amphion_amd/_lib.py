@@ -188,6 +188,12 @@ _SIGNATURES = {
     "amp_evq_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "amp_evq_check": (c_int, [c_void_p, c_void_p]),
     "amp_evq_destroy": (None, [c_void_p]),
+    "amp_dsconv_create": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_dsconv_out_len": (c_int, [c_void_p, c_int]),
+    "amp_dsconv_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_dsconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "amp_dsconv_destroy": (None, [c_void_p]),
+    "amp_gelu": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "amp_layer_norm_c_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),

@@ -1,5 +1,5 @@
 // Device building blocks shared by the split-f16 ("f16x3") MFMA kernels (conv_f16x3.hip, conv_blk_f16x3.hip, conv_small_f16x3_body.h,
-// pair_f16x3_body.h, pair_strip_f16x3.hip, rb_f16x3.hip, ampb_f16x3.hip; pw_f16x3.hip, dw_layer_f16x3.hip, codec_unit_f16x3.hip and tconv_f16x3.hip through
+// pair_f16x3_body.h, pair_strip_f16x3.hip, rb_f16x3.hip, ampb_f16x3.hip; pw_f16x3.hip, dsconv_f16x3.hip, dw_layer_f16x3.hip, codec_unit_f16x3.hip and tconv_f16x3.hip through
 // wholek_f16x3.h, which adds the blocks of the whole-K two-GEMM family; conv_mfma.hip takes the tile order and the accumulator row map).
 // Every fused form is bit-identical to the launches it replaces because all of them split an operand, form a product term and walk
 // the tiles through the SAME text: the one below.  Device code only; host declarations and argument structs are in amp_internal.h.

@@ -196,7 +196,7 @@ extern "C" {
 // points (fvq.hip, codec.hip); 147 (additive): amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add, amp_semantic_prepare;
 // 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip);
 // 149 (additive): SpeechTokenizer's amp_elu_pad (seanet.hip), amp_lstm_* (lstm.hip) and amp_evq_* (evq.hip)
-int amp_version(void) { return 149; }
+int amp_version(void) { return 150; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

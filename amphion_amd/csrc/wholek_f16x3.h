@@ -1,6 +1,6 @@
 // Device building blocks of the f16x3 kernels that contract host-packed A fragments, read from L2, against a B operand staged in LDS
-// over its whole K extent (pw_f16x3.hip per K step; dw_layer_f16x3.hip and codec_unit_f16x3.hip at once, twice, around a seam; tconv_f16x3.hip
-// at once, one GEMM, both taps one column apart in the same window):
+// over its whole K extent (pw_f16x3.hip per K step; dsconv_f16x3.hip per K step with its own three-tap A pack; dw_layer_f16x3.hip and
+// codec_unit_f16x3.hip at once, twice, around a seam; tconv_f16x3.hip at once, one GEMM, both taps one column apart in the same window):
 //   A  [row block][k16][plane hi | lo][lane] x 16 B (amp_host.h: pack_a_f16x3 with taps = 1): a wave reads the fragment pair of
 //      k-extent k of row block mb at wp[(mb * k16 + k) * 128 + lane] and + 64;
 //   B  [plane hi | lo][channel octet][column][8 x f16], S columns wide: lane (hi, l31) reads the fragment of k-extent k, column c at

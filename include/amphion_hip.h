@@ -97,7 +97,8 @@ typedef struct amp_gen amp_gen;
  * points amp_dw_*; 145 (additive): the Amphion codec entry points amp_fvq_*, amp_codec_unit_*, amp_sconv_*;
  * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
  * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
- * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*. */
+ * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*;
+ * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -823,6 +824,30 @@ int amp_evq_encode(const amp_evq* h, const float* z_dev, int B, int T, int st, i
 int amp_evq_decode(const amp_evq* h, const long long* codes_dev, int n, int st, int B, int T, float* out_dev, void* stream);
 int amp_evq_check(amp_evq* h, void* stream);
 void amp_evq_destroy(amp_evq* h);
+
+/* ---- Semantic tokenizers (models/codec/kmeans/, coco/, vevo/): RepCodec, Coco, VevoRepCodec ---- */
+
+/* Coco's down-sampling conv (csrc/dsconv_f16x3.hip; rep_coco_model.py: downsample_layers): Conv1d(cin, cout, k = 3, stride 2, padding 1),
+ *     y[b, o, t] = epi( bias[o] + sum_c sum_{j<3} w[o, c, j] x[b, c, 2t + j - 1] ),  T_out = (T - 1) / 2 + 1 (amp_dsconv_out_len:
+ * 0 for T < 1; the handle is not read and may be NULL).  epi = identity (gelu = 0) or the exact-erf GELU (gelu = 1).
+ * x [B, cin, T] -> y [B, cout, T_out], fp32; any cin, cout, T >= 1; y must not overlap x.  weight_host [cout, cin, 3], bias_host [cout] or NULL.
+ * The arithmetic is amp_set_precision's at create time.  f16x3: one kernel (host-packed weights, a two-plane staged window, each output one
+ * workgroup's sum in a fixed order; feeds the op-level range flag, see amp_range_check), no workspace (ws_dev may be NULL).
+ * AMP_PRECISION_F32: three launches inside the handle -- x copied with one zero column appended, amp_sconv's stride-2 form with the weight
+ * extended by a zero fourth tap, amp_gelu -- on ws_dev: amp_dsconv_workspace_bytes(h, B, T) bytes, 16-byte aligned.
+ * Bad arguments are AMP_ERR_INVALID and judged on the host before a device is asked for (create: NULL weight / out, cin or cout < 1, a
+ * non-finite weight); a grid overflow is AMP_ERR_UNSUPPORTED.  No allocation and no synchronisation in forward; deterministic. */
+typedef struct amp_dsconv amp_dsconv;
+int amp_dsconv_create(int cin, int cout, const float* weight_host, const float* bias_host, amp_dsconv** out);
+int amp_dsconv_out_len(const amp_dsconv* h, int T);
+size_t amp_dsconv_workspace_bytes(const amp_dsconv* h, int B, int T);
+int amp_dsconv_forward(const amp_dsconv* h, const float* x_dev, int B, int T, int gelu, void* ws_dev, size_t ws_bytes, float* y_dev, void* stream);
+void amp_dsconv_destroy(amp_dsconv* h);
+
+/* Element-wise exact-erf GELU (nn.GELU()), the function of the pointwise and down-sampling epilogues (csrc/gelu_erf.h): y[i] = gelu(x[i]),
+ * i < n.  y may alias x; any 4-byte alignment (16-byte accesses where both bases allow).  NULL pointers or n <= 0: AMP_ERR_INVALID; more than
+ * 2^31 - 1 workgroups: AMP_ERR_UNSUPPORTED; judged on the host alone. */
+int amp_gelu(const float* x_dev, long long n, float* y_dev, void* stream);
 
 #ifdef __cplusplus
 }
