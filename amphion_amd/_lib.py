@@ -102,6 +102,8 @@ _SIGNATURES = {
     "amp_gen_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "amp_set_group_mb": (c_int, [c_int]),
     "amp_set_pair_strips": (c_int, [c_int]),
+    "amp_set_strip_fit": (c_int, [c_int]),
+    "amp_pair_strip_plan": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "amp_range_check": (c_int, [c_void_p]),
     "amp_gen_range_check": (c_int, [c_void_p, c_void_p]),
     "amp_gen_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -82,6 +82,7 @@ constexpr int kConvRgFastDefault = 1;
 constexpr int kPingPongDefault = 1;
 struct Config {
     int pair_strips = -1;      // -1 policy, 0 per-tile kernel, 1 four-wave strips
+    int strip_fit = -1;        // fitted strips of the fused-pair strip kernel: -1 the plan (strip_geometry, conv_host.hip), 0 never, 1 every strip launch
     int rb_fusion = 1;
     int ampb_fusion = 1;
     int conv_blk = kConvBlkDefault;
@@ -184,6 +185,7 @@ int next_rev(const int* lens);
 bool pair_supported(const amp_conv* c1, const amp_conv* c2);
 int pair_run(const amp_conv* c1, const amp_conv* c2, const float* x, int B, int T, float slope, float* y, int mode, float div,
              hipStream_t stream, const int* lens = nullptr, int len_mul = 1);
+bool pair_strip_plan(int B, int T, int k, bool ragged, int* form, int* strip_len, int* spi, int* steps);
 bool pair_tile_args(const amp_conv* c1, const amp_conv* c2, const float* x, int B, int T, float slope, float* y, int mode, float div,
                     const int* lens, int len_mul, PairArgs* out);
 

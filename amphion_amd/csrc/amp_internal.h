@@ -83,6 +83,8 @@ struct PairArgs {
     int strip_len;             // strip kernel (pair_strip_f16x3.hip): output columns per workgroup ...
     int strips_per_item;       // ... and workgroups per batch item, ceil(T / strip_len)
     int wide;                  // strip kernel: 0 = four-wave strips, 3 = the 2 x 2-blocked A-ring form (one workgroup per CU)
+    int fit;                   // strip kernel: 1 = fitted strips (outputs start at the strip's first column, a halo prologue computes the k - 1
+                               // carried xt columns), 0 = shifted strips (a strip starts k - 1 columns early and discards them)
     int rev;                   // 1: descending tile / strip order, see ConvArgs::rev
     int dil;
     float slope;               // leaky_relu slope (on x while staging, on conv1's output at the seam)
@@ -384,6 +386,20 @@ inline void note_kernel(const char* base, A... args) {
     if (tl_kernel_log->find(buf) != std::string::npos) return;
     if (!tl_kernel_log->empty()) *tl_kernel_log += " | ";
     *tl_kernel_log += buf;
+}
+// after note_kernel(): a form of the kernel that is a launch argument, not a template argument -- appended once to the kernel log only
+// (the manifest keeps the profiler's spelling of the name and states the form in note_work's description)
+inline void note_form(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+inline void note_form(const char* fmt, ...) {
+    if (!tl_kernel_log) return;
+    char form[64];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(form, sizeof(form), fmt, ap);
+    va_end(ap);
+    if (tl_kernel_log->find(form) != std::string::npos) return;
+    *tl_kernel_log += " ";
+    *tl_kernel_log += form;
 }
 // after note_kernel(): the launch's grid and algorithmic work (manifest only)
 inline void note_work(unsigned long long workgroups, double gflop, double mb, const char* fmt, ...) __attribute__((format(printf, 4, 5)));

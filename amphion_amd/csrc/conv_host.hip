@@ -130,13 +130,58 @@ static void strip_plan(int B, int T, int n1, int hb, int wg_per_cu, int* strip_l
 // times over -- the k - 1 columns a strip computes and throws away and the pipeline fill are paid once per 1 014 outputs instead of
 // once per 246: -1 % per launch at B = 64, T = 16 384 (k = 11: 1.928 -> 1.892 ms), same bits (every output's operation order is that of
 // any other cut, tests/test_gpu_pair.py).  Ragged batches keep the one-step strips they were measured with.
-static void strip_geometry(int B, int T, int n1, int hb, int wg_per_cu, int steps, bool ragged, int* strip_len, int* spi) {
+//
+// Fitted strips (PairArgs::fit): a strip of S steps keeps all S * n1 columns it computes and pays a halo prologue of kFitPrologueSteps
+// instead of the k - 1 discarded columns (0.04 of a step).  That only pays where it saves a whole round of workgroups: at B = 64,
+// T = 16 384 an item is exactly 64 steps, the shifted strips cut it into 16 x 4 + 1 steps (1 088 workgroups, 4 160 steps: a 17th round of
+// steps on a quarter of the CUs), the fitted ones into 64 (4 096 steps: 16 rounds).  Both forms go through ONE cost model, rounds of
+// workgroups x (steps per strip [+ the prologue]) + the quarter-step fill per workgroup; the shifted form at today's step count, the
+// fitted form at four and eight steps per strip, and only where the shifted plan already walks four-step strips (the same "fills the chip
+// four times over" guard) and 512+ fitted strips remain (pair_run hands smaller grids to the per-tile kernel).  A tie keeps the shifted
+// form.  amp_set_strip_fit: -1 this plan, 0 never, 1 every strip launch (the shifted plan's step count, fitted; ragged batches too).
+// Same bits either way (tests/test_gpu_pair_strip_fit.py).
+constexpr double kFitPrologueSteps = 0.2;    // m, in steps: measured 0.17 - 0.19 with four-step strips, 0.22 - 0.23 derived from eight-step ones (profiles/r7_strip_fit.txt)
+static void strip_geometry(int B, int T, int n1, int hb, int wg_per_cu, int steps, bool ragged, int* strip_len, int* spi, int* fit) {
+    *fit = 0;
     strip_plan(B, T, n1, hb, wg_per_cu, strip_len, spi);
     if (steps > 0 && steps * n1 - hb < T) { *strip_len = steps * n1 - hb; *spi = (T + *strip_len - 1) / *strip_len; }
+    bool four = false;
     if (steps == 1 && !ragged && 4 * n1 - hb < T) {
         const int len4 = 4 * n1 - hb, spi4 = (T + len4 - 1) / len4;
-        if ((long long)B * spi4 >= 1024) { *strip_len = len4; *spi = spi4; }
+        if ((long long)B * spi4 >= 1024) { *strip_len = len4; *spi = spi4; four = true; }
     }
+    const int mode = cfg().strip_fit;
+    if (mode == 0) return;
+    if (mode == 1) {
+        const int st = (*strip_len + hb + n1 - 1) / n1;
+        *strip_len = st * n1; *spi = (T + *strip_len - 1) / *strip_len; *fit = 1;
+        return;
+    }
+    if (!four) return;
+    const long long slots = (long long)wg_per_cu * 256;
+    auto rounds = [&](int nspi) { return ((long long)B * nspi + slots - 1) / slots; };
+    auto cost = [&](int nspi, double steps_per_strip) { return (double)rounds(nspi) * (4.0 * steps_per_strip + 1.0); };
+    double best = cost(*spi, 4.0);
+    const long long shifted_rounds = rounds(*spi) * 4;
+    for (int S : {4, 8}) {
+        const int len = S * n1, nspi = (T + len - 1) / len;
+        if (len > T || (long long)B * nspi < 512) continue;
+        if (rounds(nspi) * S >= shifted_rounds) continue;      // no whole round of steps saved: the model's fill term alone (one fill per eight steps) is not a measured gain
+        const double c = cost(nspi, S + kFitPrologueSteps);
+        if (c < best) { best = c; *strip_len = len; *spi = nspi; *fit = 1; }
+    }
+}
+
+// The plan alone, for tests and tools: the strips a fused C = 128 pair of kernel k would be cut into at (B, T) under the current switches.
+// form: 0 shifted, 1 fitted; steps = steps per full strip; false when (k) has no strip kernel.
+bool pair_strip_plan(int B, int T, int k, bool ragged, int* form, int* strip_len, int* spi, int* steps) {
+    int wg = 2;
+    const StripChoice sc = strip_choice(128, k);
+    const int n1 = sc.use ? strip_step(k, 128, 1, sc.wide, &wg) : 0;
+    if (n1 <= 0) return false;
+    strip_geometry(B, T, n1, k - 1, wg, sc.steps, ragged, strip_len, spi, form);
+    *steps = (*strip_len + (*form ? 0 : k - 1) + n1 - 1) / n1;
+    return true;
 }
 
 // Half-width conv tiles (NI = 2) for launches that would leave most CUs idle (a single utterance): conv_run()
@@ -405,7 +450,7 @@ int pair_run(const amp_conv* c1, const amp_conv* c2, const float* x, int B, int 
     const int n1 = sc.use ? strip_step(c1->k, c1->cin, c1->dilation, sc.wide, &wg) : 0;
     if (n1 > 0) {
         a.wide = sc.wide;
-        strip_geometry(B, T, n1, c1->k - 1, wg, sc.steps, lens != nullptr, &a.strip_len, &a.strips_per_item);
+        strip_geometry(B, T, n1, c1->k - 1, wg, sc.steps, lens != nullptr, &a.strip_len, &a.strips_per_item, &a.fit);
         // one workgroup per CU: a grid that cannot fill the chip twice over (a single utterance) is better served by the
         // 4x as many independent tiles of the per-tile kernel (same bits)
         if (cfg().pair_strips == -1 && sc.wide >= 2 && (long long)B * a.strips_per_item < 512 && pair_tile(c1->k, c1->cin, c1->dilation) > 0) {
@@ -444,8 +489,8 @@ bool pair_tile_args(const amp_conv* c1, const amp_conv* c2, const float* x, int 
     const StripChoice sc = strip_choice(c1->cin, c1->k);
     const int n1 = sc.use ? strip_step(c1->k, c1->cin, c1->dilation, sc.wide, &wg) : 0;
     if (n1 > 0) {       // pair_run's rule: the strips unless the grid cannot fill the chip twice over
-        int strip_len = 0, strips_per_item = 0;
-        strip_geometry(B, T, n1, c1->k - 1, wg, sc.steps, lens != nullptr, &strip_len, &strips_per_item);
+        int strip_len = 0, strips_per_item = 0, fit = 0;
+        strip_geometry(B, T, n1, c1->k - 1, wg, sc.steps, lens != nullptr, &strip_len, &strips_per_item, &fit);
         if (!(cfg().pair_strips == -1 && sc.wide >= 2 && (long long)B * strips_per_item < 512)) return false;
     }
     const int NT = pair_tile(c1->k, c1->cin, c1->dilation);

@@ -17,7 +17,9 @@
 //   epilogue  the staging loads of the NEXT step's first chunk are issued, then + bias, + residual x, MRF
 //             accumulate, store.
 //
-// Only the first step of a strip computes KT - 1 columns it throws away.  Per output element the order of
+// Only the first step of a strip computes KT - 1 columns it throws away -- or none (round 7, PairArgs::fit): a FITTED strip starts its outputs at
+// its first column and computes the KT - 1 carried xt columns in a halo prologue (below, before the step loop), so that an utterance whose length
+// is a multiple of the step is cut into whole steps (conv_host.hip strip_geometry chooses per shape; profiles/r7_strip_fit.txt).  Per output element the order of
 // operations (bias, chunks, taps, the three MFMAs of a term) is that of the per-tile kernel and of
 // conv_f16x3.hip, so the result has the same bits however the time axis is cut (tests/test_gpu_pair.py).
 //
@@ -94,7 +96,10 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     // downstream reads them (a batch of 60..400-frame utterances is 40 % such columns); the steps before keep their positions
     const int Oend = O + a.strip_len < Tv ? O + a.strip_len : Tv;
     if (O >= Oend) return;                    // workgroup-uniform
-    const int nsteps = (Oend - O + HB + N1 - 1) / N1;
+    // a.fit (fitted strips): the outputs of step 0 start at O itself -- a halo prologue computes the HB xt columns in front of them --
+    // so a strip of `len` outputs is ceil(len / N1) steps and keeps every column it computes
+    const bool fit = a.fit != 0;              // workgroup-uniform
+    const int nsteps = (Oend - O + (fit ? 0 : HB) + N1 - 1) / N1;
     const int dil = a.dil;
     const int h1 = H2 * dil;
 
@@ -127,11 +132,14 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     gf_ptr yr_s = (gf_ptr)yr;
     float range_max = 0.f;       // largest |staged operand| (x16 applied): beyond 65504 it left the f16 range (a.range_flag)
     float xs[NST][4];
-    auto stage_load = [&](int chunk, int tbase) {
+    // pro: the halo prologue of a fitted strip stages only the 64-column groups its one n-tile reads, [N1 - 32, N1 + 2 * h1)
+    auto pro_skip = [&](int cb) { return cb + 64 <= N1 - 32 || cb >= N1 + 2 * h1; };   // wave-uniform
+    auto stage_load = [&](int chunk, int tbase, bool pro = false) {
 #pragma unroll
         for (int it = 0; it < NST; ++it) {
             const int ibase = wave * 64 + NTHR * it;         // wave-uniform
             const int qd = ibase / SX;                       // channel quad 0..3
+            if (pro && pro_skip(ibase - qd * SX)) continue;
             const int col = ibase - qd * SX + lane;
             int t = tbase + col;
             t = t < 0 ? 0 : t;
@@ -141,12 +149,13 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
             for (int e = 0; e < 4; ++e) xs[it][e] = xb[(size_t)(ch0 + e) * Ts + t];
         }
     };
-    auto stage_store = [&](int buf, int tbase) {
+    auto stage_store = [&](int buf, int tbase, bool pro = false) {
         uint2* dst = reinterpret_cast<uint2*>(smem4 + buf * XBUF);
 #pragma unroll
         for (int it = 0; it < NST; ++it) {
             const int ibase = wave * 64 + NTHR * it;
             const int qd = ibase / SX;
+            if (pro && pro_skip(ibase - qd * SX)) continue;
             const int col = ibase - qd * SX + lane;
             const int t = tbase + col;
             const bool tok = (t >= 0) && (t < Tv);
@@ -179,8 +188,9 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
     const int rd1 = hi * SX + colw;
     const int rd2 = hi * XT + colw;
 
-    int X = O - H2;                           // first xt column of the step
-    stage_load(0, X - h1);
+    int X = fit ? O + H2 : O - H2;            // first xt column of the step
+    if (fit) stage_load(0, X - N1 - h1, true);
+    else stage_load(0, X - h1);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -189,6 +199,81 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
             a_l[mi][g].u = wa1[mi * MBS + g * 128 + 64];
         }
     AMP_PIN_VMEM();
+
+    // ---------------- halo prologue of a fitted strip ----------------
+    // conv1 of the step that would have ended at X, for its last n-tile only: xt columns [X - 32, X).  Its seam leaves the tile where a
+    // previous step would have: step 0's carry move finds the HB columns there (behind step 0's barriers: the lane that moves them is not
+    // the one that wrote them here).  Same chunk / tap / hh, hl, lh order per element as a full step; tok / qok pad at the item's ends.
+    // The tile's MI row blocks of wave row wm are shared among its WN waves (row block pm = wn), and a wave holds a WHOLE chunk of A
+    // fragments of its row block, reloaded one chunk ahead: a tap is 3 MFMAs here, and the ring of the steps (RING taps ahead: 12 MFMAs per
+    // tap there) would wait for L2 at every tap.  The ring itself is not touched: step 0 finds conv1's first taps in it.
+    if (fit) {
+        static_assert(MI == WN, "the prologue hands one row block of the tile to each wave of a wave row");
+        const int pm = wn;
+        const int pcol = N1 - 32 + l31;       // this lane's xt column of the prologue step
+        const int tbase = X - N1 - h1;
+        const float* bias1 = a.bias1;
+        f32x16 accp;
+        {
+            const float s1 = a.sc1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) accp[r] = bias1[32 * (MI * wm + pm) + 16 * hi + r] * s1;
+        }
+        Frag pa_h[KT], pa_l[KT];
+        const uint4* wp = wa1 + (size_t)pm * MBS;
+#pragma unroll
+        for (int g = 0; g < KT; ++g) {
+            pa_h[g].u = wp[g * 128];
+            pa_l[g].u = wp[g * 128 + 64];
+        }
+        AMP_PIN_VMEM();
+        stage_store(0, tbase, true);
+        __syncthreads();
+#pragma unroll 1
+        for (int c = 0; c < NCH; ++c) {
+            const bool more = (c + 1) < NCH;
+            stage_load(more ? c + 1 : c, tbase, true);
+            AMP_PIN_VMEM();
+            const uint4* wnext = wp + (size_t)(more ? c + 1 : c) * (KT * 128);      // last chunk: a read nobody uses
+            const uint4* base = smem4 + (SBUF == 2 ? (c & 1) : 0) * XBUF + hi * SX + pcol;
+            Frag bh[2][1], bl[2][1];
+            bh[0][0].u = base[0];
+            bl[0][0].u = base[2 * SX];
+#pragma unroll
+            for (int g = 0; g < KT; ++g) {
+                const int cur = g & 1;
+                if (g + 1 < KT) {
+                    bh[cur ^ 1][0].u = base[(g + 1) * dil];
+                    bl[cur ^ 1][0].u = base[(g + 1) * dil + 2 * SX];
+                }
+                AMP_PIN_DSREAD();
+                mfma3<1>(&accp, pa_h[g], pa_l[g], bh[cur], bl[cur]);
+                pa_h[g].u = wnext[g * 128];
+                pa_l[g].u = wnext[g * 128 + 64];
+                AMP_PIN_VMEM();
+            }
+            if (SBUF == 1) __syncthreads();   // every wave has read the one staging buffer
+            if (more) stage_store(SBUF == 2 ? (c + 1) & 1 : 0, tbase, true);
+            __syncthreads();
+        }
+        stage_load(0, X - h1);                // step 0's first chunk lands under the seam
+        AMP_PIN_VMEM();
+        {
+            const float i1 = a.isc1;
+            const float slope = a.slope;
+            const int q = X - N1 + pcol;
+            const bool qok = (q >= 0) && (q < Tv);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                struct { uint2 u; } fh0, fl0, fh1, fl1;
+                seam4_f16(accp[8 * o + 0], accp[8 * o + 1], accp[8 * o + 2], accp[8 * o + 3], i1, slope, qok, range_max, fh0.u, fl0.u);
+                seam4_f16(accp[8 * o + 4], accp[8 * o + 5], accp[8 * o + 6], accp[8 * o + 7], i1, slope, qok, range_max, fh1.u, fl1.u);
+                const int o4 = (2 * (MI * wm + pm) + hi) * XTCH + o * XT + HB + pcol;
+                xt4[o4] = make_uint4(fh0.u.x, fh0.u.y, fh1.u.x, fh1.u.y);
+                xt4[o4 + 2 * XT] = make_uint4(fl0.u.x, fl0.u.y, fl1.u.x, fl1.u.y);
+            }
+        }
+    }
 
 #pragma clang loop unroll(disable)
     for (int s = 0; s < nsteps; ++s, X += N1) {
@@ -287,7 +372,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MI > 1 ? 1 : 2)) void pair_strip_ker
         {
             // position of xt column `col` of this step = HB + col.  The lane that wrote column col >= N1 - HB in the
             // previous step moves it from HB + col to HB + col - N1 before overwriting it (own data, in order).
-            if (s > 0 && wn == WN - 1) {
+            if ((s > 0 || fit) && wn == WN - 1) {
                 const int col = colw + 32 * (NI - 1);
                 if (col >= N1 - HB) {
 #pragma unroll
@@ -428,9 +513,13 @@ static hipError_t launch_strip_one(const PairArgs& a, hipStream_t stream) {
     const size_t lds = ((size_t)SBUF * 4 * SX + (size_t)2 * WM * MI * 4 * XT) * sizeof(uint4);
     if (hipError_t e = ensure_dynamic_lds<&pair_strip_kernel<KT, WM, WN, NI, SX, MI, RING, SBUF>>(lds); e != hipSuccess) return e;
     dim3 grid((unsigned)(a.B * a.strips_per_item));
+    // the strip form is an argument, not a template parameter: the kernel log (amp_gen_kernel_name) carries it behind the name, the manifest
+    // in its description -- the manifest's name column stays the profiler's spelling, which tools/roofline_table.py joins on
+    const int steps = (a.strip_len + (a.fit ? 0 : KT - 1) + N1 - 1) / N1;
     note_kernel("pair_strip_kernel", KT, WM, WN, NI, SX, MI, RING, SBUF);
+    if (a.fit) note_form("[fitted strips, %d steps]", steps);
     note_work(grid.x, 2 * 2.0 * a.C * a.C * KT * (double)a.T * a.B / 1e9, 2 * 4.0 * a.B * (double)a.C * a.T * (1.0 + (a.mode ? 0.5 : 0.0)) / 1e6,
-              "fused pair C=%d k=%d d=%d T=%d B=%d%s", a.C, KT, a.dil, a.T, a.B, a.mode ? " +sum" : "");
+              "fused pair C=%d k=%d d=%d T=%d B=%d%s %s strips of %d steps", a.C, KT, a.dil, a.T, a.B, a.mode ? " +sum" : "", a.fit ? "fitted" : "shifted", steps);
     hipLaunchKernelGGL((pair_strip_kernel<KT, WM, WN, NI, SX, MI, RING, SBUF>), grid, dim3(64 * WM * WN), lds, stream, a);
     return hipGetLastError();
 }

@@ -195,8 +195,9 @@ extern "C" {
 // amp_istft_same_polar, amp_dwconv_layer_norm_c takes K = 7; 144 (additive): the DiffWave entry points amp_dw_* (diffwave.hip); 145 / 146 (additive): the codec entry
 // points (fvq.hip, codec.hip); 147 (additive): amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add, amp_semantic_prepare;
 // 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip);
-// 149 (additive): SpeechTokenizer's amp_elu_pad (seanet.hip), amp_lstm_* (lstm.hip) and amp_evq_* (evq.hip)
-int amp_version(void) { return 150; }
+// 149 (additive): SpeechTokenizer's amp_elu_pad (seanet.hip), amp_lstm_* (lstm.hip) and amp_evq_* (evq.hip); 150 (additive): amp_dsconv_* and amp_gelu;
+// 151 (additive): amp_set_strip_fit and amp_pair_strip_plan (fitted strips of the fused-pair strip kernel, conv_host.hip strip_geometry)
+int amp_version(void) { return 151; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {
@@ -219,6 +220,18 @@ int amp_device_count(void) {
 int amp_set_pair_strips(int on) {
     if (on < -1 || on > 0) { set_error("amp_set_pair_strips: %d (-1 the policy, 0 the per-tile kernel everywhere; the four-wave strips of mode 1 left in ABI 142)", on); return AMP_ERR_INVALID; }
     cfg().pair_strips = on;
+    return AMP_OK;
+}
+
+int amp_set_strip_fit(int mode) {
+    if (mode < -1 || mode > 1) { set_error("amp_set_strip_fit: %d (-1 the plan, 0 never: shifted strips, 1 every strip launch)", mode); return AMP_ERR_INVALID; }
+    cfg().strip_fit = mode;
+    return AMP_OK;
+}
+
+int amp_pair_strip_plan(int B, int T, int k, int ragged, int* form, int* strip_len, int* strips_per_item, int* steps) {
+    if (B < 1 || T < 1 || !form || !strip_len || !strips_per_item || !steps) { set_error("amp_pair_strip_plan: B=%d T=%d or a null result pointer", B, T); return AMP_ERR_INVALID; }
+    if (!pair_strip_plan(B, T, k, ragged != 0, form, strip_len, strips_per_item, steps)) { set_error("amp_pair_strip_plan: no strip kernel for k=%d", k); return AMP_ERR_UNSUPPORTED; }
     return AMP_OK;
 }
 

@@ -98,7 +98,7 @@ typedef struct amp_gen amp_gen;
  * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
  * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
  * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*;
- * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu. */
+ * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -155,6 +155,14 @@ int amp_gen_range_check(amp_gen* g, void* stream);
  * LDS; C = 128, k >= 7, launches that fill the chip).  -1 (default): the measured per-shape policy; 0: per-tile
  * everywhere (the cross-check).  Mode 1 (four-wave / C = 256 strips) left with amp_version 142. */
 int amp_set_pair_strips(int on);
+/* The strip-mined kernel cuts an utterance into strips in one of two forms, bit-identical (tests/test_gpu_pair_strip_fit.py): SHIFTED strips
+ * start k - 1 columns early and discard them (S * 256 - (k - 1) outputs per S steps), FITTED strips keep every column of every step and
+ * compute the k - 1 carried columns in a short prologue -- cheaper exactly where that saves a round of workgroups (T a multiple of the step).
+ * -1 (default): the cost model of strip_geometry (conv_host.hip) chooses per (B, T, k); 0: never; 1: every strip launch.
+ * amp_pair_strip_plan reports the plan of a C = 128 pair at (B, T, k) under the current switches, without a device: form 0 shifted / 1 fitted,
+ * outputs per strip, strips per item and steps per full strip; AMP_ERR_UNSUPPORTED when kernel size k has no strip kernel. */
+int amp_set_strip_fit(int mode);
+int amp_pair_strip_plan(int B, int T, int k, int ragged, int* form, int* strip_len, int* strips_per_item, int* steps);
 
 /* Replaces HiFiGAN.forward (hifigan.py:203-219), BigVGAN.forward (bigvgan.py:313-331) and
  * HiFiGAN_vits.forward (hifigan.py:424-443):  mel_dev [B, n_in, T]  ->  wav_dev [B, 1, T*hop].
