@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.quantize import FactorizedVectorQuantize, ResidualVQ  # noqa: F401
 from amphion_amd.models.codec.amphion_codec.vocos import Vocos, _check_input, _check_tensors
@@ -33,14 +34,6 @@ from amphion_amd.modules.hip_ops import HipConv1d
 
 def WNConv1d(*args, **kwargs):
     return HipConv1d(*args, **kwargs)
-
-
-def _host(t):
-    return t.detach().to("cpu", torch.float32).contiguous()
-
-
-def _sig(params, device):
-    return tuple((p.data_ptr(), p._version) for p in params) + (str(device), _lib.get_precision())
 
 
 def snake(x, alpha):
@@ -80,21 +73,18 @@ class ResidualUnit(nn.Module):
         pad = ((7 - 1) * dilation) // 2
         self.dim, self.dilation = dim, dilation
         self.block = nn.Sequential(Snake1d(dim), WNConv1d(dim, dim, 7, dilation=dilation, padding=pad), Snake1d(dim), WNConv1d(dim, dim, 1))
-        self._h, self._hsig, self._fin = None, None, None
+        self._cache = HandleCache("amp_codec_unit_destroy")
 
     def _handle(self, device):
+        return self._cache.get(param_sig(self.parameters(), str(device), _lib.get_precision()), self._build, device)
+
+    def _build(self, device):
         a1, c1, a2, c2 = self.block
-        sig = _sig(list(self.parameters()), device)
-        if self._h is not None and sig == self._hsig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        t = [_host(a1.alpha).reshape(-1), _host(c1.folded_weight()), _host(c1.bias), _host(a2.alpha).reshape(-1), _host(c2.folded_weight()),
-             _host(c2.bias)]
+        t = [host_f32(a1.alpha).reshape(-1), host_f32(c1.folded_weight()), host_f32(c1.bias), host_f32(a2.alpha).reshape(-1),
+             host_f32(c2.folded_weight()), host_f32(c2.bias)]
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_codec_unit_create(self.dim, self.dilation, *[_p(v) for v in t], ctypes.byref(h)))
-        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_codec_unit_destroy", h)
         return h
 
     def fused(self, device):
@@ -124,19 +114,16 @@ class _StridedConv(ConvParams):
 
     def __init__(self, cin, cout, stride, padding):
         super().__init__(cin, cout, 2 * stride, stride=stride, padding=padding)
-        self._h, self._hsig, self._fin = None, None, None
+        self._cache = HandleCache("amp_sconv_destroy")
 
     def _handle(self, device):
-        sig = _sig([p for p in self._parameters.values() if p is not None], device)
-        if self._h is not None and sig == self._hsig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w, b = _host(self.folded_weight()), _host(self.bias)
+        return self._cache.get(param_sig(self._parameters.values(), str(device), _lib.get_precision()), self._build, device)
+
+    def _build(self, device):
+        w, b = host_f32(self.folded_weight()), host_f32(self.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_sconv_create(self.cin, self.cout, self.stride, self.padding, _p(w), _p(b), ctypes.byref(h)))
-        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_sconv_destroy", h)
         return h
 
     def forward(self, x, alpha=None):
@@ -165,19 +152,16 @@ class _TransposedConv(ConvParams):
     def __init__(self, cin, cout, stride, padding, output_padding=0):
         super().__init__(cin, cout, 2 * stride, transposed=True, stride=stride, padding=padding)
         self.output_padding = output_padding
-        self._h, self._hsig, self._fin = None, None, None
+        self._cache = HandleCache("amp_tconv_destroy")
 
     def _handle(self, device):
-        sig = _sig([p for p in self._parameters.values() if p is not None], device)
-        if self._h is not None and sig == self._hsig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w, b = _host(self.folded_weight()), _host(self.bias)
+        return self._cache.get(param_sig(self._parameters.values(), str(device), _lib.get_precision()), self._build, device)
+
+    def _build(self, device):
+        w, b = host_f32(self.folded_weight()), host_f32(self.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_tconv_create(self.cin, self.cout, self.stride, self.padding, self.output_padding, _p(w), _p(b), ctypes.byref(h)))
-        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_tconv_destroy", h)
         return h
 
     def fused(self, device):

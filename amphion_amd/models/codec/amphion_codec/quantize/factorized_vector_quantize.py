@@ -10,6 +10,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32_array, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.modules.hip_ops import HipConv1d
 
@@ -25,39 +26,26 @@ class FvqHandle:
 
     def __init__(self, project=True):
         self.project = project
-        self._h, self._sig, self._fin = None, None, None
+        self._cache = HandleCache("amp_fvq_destroy")
 
     def get(self, levels, device):
-        sig = tuple((p.data_ptr(), p._version) for q in levels for p in q.parameters()) + (str(device), len(levels))
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
+        return self._cache.get(param_sig([p for q in levels for p in q.parameters()], str(device), len(levels)), self._build, levels, device)
+
+    def _build(self, levels, device):
         q0 = levels[0]
-        proj = self.project and q0.input_dim != q0.codebook_dim
-        keep = []
-
-        def host(t):
-            t = t.detach().to("cpu", torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        n = len(levels)
-        arr = lambda vals: (ctypes.c_void_p * n)(*vals)     # noqa: E731
-        cb = arr([host(q.codebook.weight) for q in levels])
-        if proj:
-            wi = arr([host(q.in_project.folded_weight()) for q in levels])
-            bi = arr([host(q.in_project.bias) for q in levels])
-            wo = arr([host(q.out_project.folded_weight()) for q in levels])
-            bo = arr([host(q.out_project.bias) for q in levels])
+        cb = host_f32_array([q.codebook.weight for q in levels])
+        if self.project and q0.input_dim != q0.codebook_dim:
+            wi = host_f32_array([q.in_project.folded_weight() for q in levels])
+            bi = host_f32_array([q.in_project.bias for q in levels])
+            wo = host_f32_array([q.out_project.folded_weight() for q in levels])
+            bo = host_f32_array([q.out_project.bias for q in levels])
         else:
             wi = bi = wo = bo = None
         h = ctypes.c_void_p()
         D = q0.input_dim if self.project else q0.codebook_dim
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().amp_fvq_create(D, q0.codebook_dim, q0.codebook_size, n, int(bool(q0.use_l2_normlize)), wi, bi, cb, wo, bo,
+            _lib.check(_lib.lib().amp_fvq_create(D, q0.codebook_dim, q0.codebook_size, len(levels), int(bool(q0.use_l2_normlize)), wi, bi, cb, wo, bo,
                                                  ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_fvq_destroy", h)
         return h
 
 

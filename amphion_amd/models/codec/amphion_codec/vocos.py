@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.modules.hip_ops import HipConv1d
 
@@ -40,21 +41,16 @@ class _PwHandle:
     change (a handle keeps the arithmetic it was created with)."""
 
     def __init__(self):
-        self._h, self._sig, self._fin = None, None, None
+        self._cache = HandleCache("amp_pw_destroy")
 
     def get(self, lin: nn.Linear, device):
-        prec = _lib.get_precision()
-        sig = tuple((p.data_ptr(), p._version) for p in (lin.weight, lin.bias) if p is not None) + (str(device), prec)
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w = lin.weight.detach().to("cpu", torch.float32).contiguous()
-        b = lin.bias.detach().to("cpu", torch.float32).contiguous() if lin.bias is not None else None
+        return self._cache.get(param_sig((lin.weight, lin.bias), str(device), _lib.get_precision()), self._build, lin, device)
+
+    def _build(self, lin, device):
+        w, b = host_f32(lin.weight), host_f32(lin.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_pw_create(lin.in_features, lin.out_features, _p(w), _p(b), ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_pw_destroy", h)
         return h
 
 

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.quantize import ResidualVQ
 from amphion_amd.models.codec.amphion_codec.vocos import _check_input, _check_tensors, _PwHandle, pw_forward
@@ -40,20 +41,16 @@ class DownsampleConv1d(nn.Conv1d):
 
     def __init__(self, cin, cout):
         super().__init__(cin, cout, kernel_size=3, stride=2, padding=1)
-        self._h, self._sig, self._fin = None, None, None
+        self._cache = HandleCache("amp_dsconv_destroy")
 
     def _ensure(self, device):
-        sig = tuple((p.data_ptr(), p._version) for p in (self.weight, self.bias)) + (str(device), _lib.get_precision())
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w = self.weight.detach().to("cpu", torch.float32).contiguous()
-        b = self.bias.detach().to("cpu", torch.float32).contiguous()
+        return self._cache.get(param_sig((self.weight, self.bias), str(device), _lib.get_precision()), self._build, device)
+
+    def _build(self, device):
+        w, b = host_f32(self.weight), host_f32(self.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_dsconv_create(self.in_channels, self.out_channels, _p(w), _p(b), ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_dsconv_destroy", h)
         return h
 
     def forward(self, x, gelu=False):

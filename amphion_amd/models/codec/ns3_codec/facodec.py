@@ -31,8 +31,9 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
-from amphion_amd.models.codec.amphion_codec.codec import _check_channels, _host, _sig, _StridedConv, _TransposedConv
+from amphion_amd.models.codec.amphion_codec.codec import _check_channels, _StridedConv, _TransposedConv
 from amphion_amd.models.codec.amphion_codec.vocos import _check_input, _check_tensors
 from amphion_amd.models.vocoders.gan.generator._engine import ConvParams
 from amphion_amd.modules.activation_functions.snake import SnakeBeta
@@ -71,25 +72,23 @@ class ResidualUnit(nn.Module):
         pad = ((7 - 1) * dilation) // 2
         self.dim, self.dilation = dim, dilation
         self.block = nn.Sequential(_aa(dim), WNConv1d(dim, dim, 7, dilation=dilation, padding=pad), _aa(dim), WNConv1d(dim, dim, 1))
-        self._h, self._hsig, self._fin = None, None, None
+        self._cache = HandleCache("amp_aa_unit_destroy")
 
     def _handle(self, device):
+        sig = param_sig(list(self.parameters()) + list(self.buffers()), str(device), _lib.get_precision())
+        return self._cache.get(sig, self._build, device)
+
+    def _build(self, device):
         a1, c1, a2, c2 = self.block
-        sig = _sig(list(self.parameters()) + list(self.buffers()), device)
-        if self._h is not None and sig == self._hsig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        beta1 = _host(a1.act.beta) if getattr(a1.act, "has_beta", False) else None
-        beta2 = _host(a2.act.beta) if getattr(a2.act, "has_beta", False) else None
-        t = [_host(a1.act.alpha), beta1, _host(c1.folded_weight()), _host(c1.bias), _host(a2.act.alpha), beta2, _host(c2.folded_weight()),
-             _host(c2.bias)]
-        fu, fd = _host(a1.upsample.filter).reshape(-1), _host(a1.downsample.lowpass.filter).reshape(-1)
+        beta1 = host_f32(a1.act.beta) if getattr(a1.act, "has_beta", False) else None
+        beta2 = host_f32(a2.act.beta) if getattr(a2.act, "has_beta", False) else None
+        t = [host_f32(a1.act.alpha), beta1, host_f32(c1.folded_weight()), host_f32(c1.bias), host_f32(a2.act.alpha), beta2,
+             host_f32(c2.folded_weight()), host_f32(c2.bias)]
+        fu, fd = host_f32(a1.upsample.filter).reshape(-1), host_f32(a1.downsample.lowpass.filter).reshape(-1)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_aa_unit_create(self.dim, self.dilation, *[_p(v) for v in t], int(a1.act.alpha_logscale), _p(fu), _p(fd),
                                                      ctypes.byref(h)))
-        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_aa_unit_destroy", h)
         return h
 
     def fused(self, device):

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32_array, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.quantize.factorized_vector_quantize import _no_training
 
@@ -58,41 +59,26 @@ class Handle:
     """The device copy of a stack of levels for ``amp_fvq_*``, rebuilt when a parameter or the device changes"""
 
     def __init__(self):
-        self._h, self._sig, self._fin = None, None, None
-
-    def __deepcopy__(self, memo):
-        return Handle()
+        self._cache = HandleCache("amp_fvq_destroy")
 
     def get(self, levels, device):
-        sig = tuple((p.data_ptr(), p._version) for q in levels for p in q.parameters()) + (str(device), len(levels))
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        keep = []
+        return self._cache.get(param_sig([p for q in levels for p in q.parameters()], str(device), len(levels)), self._build, levels, device)
 
-        def host(t):
-            t = t.detach().to("cpu", torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        n = len(levels)
-        arr = lambda vals: (ctypes.c_void_p * n)(*vals)     # noqa: E731
+    def _build(self, levels, device):
         q0 = levels[0]
         if any((q.dim, q.codebook_dim, q.codebook_size) != (q0.dim, q0.codebook_dim, q0.codebook_size) for q in levels):
             raise NotImplementedError("ResidualVQ: levels whose codebook sizes differ are not on the HIP path (one kernel walks all levels)")
-        cb = arr([host(q._codebook.weight) for q in levels])
+        cb = host_f32_array([q._codebook.weight for q in levels])
         if q0.dim != q0.codebook_dim:
-            wi = arr([host(q.in_proj.folded_weight()) for q in levels])
-            bi = arr([host(q.in_proj.bias) for q in levels])
-            wo = arr([host(q.out_proj.folded_weight()) for q in levels])
-            bo = arr([host(q.out_proj.bias) for q in levels])
+            wi = host_f32_array([q.in_proj.folded_weight() for q in levels])
+            bi = host_f32_array([q.in_proj.bias for q in levels])
+            wo = host_f32_array([q.out_proj.folded_weight() for q in levels])
+            bo = host_f32_array([q.out_proj.bias for q in levels])
         else:
             wi = bi = wo = bo = None
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().amp_fvq_create(q0.dim, q0.codebook_dim, q0.codebook_size, n, 1, wi, bi, cb, wo, bo, ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_fvq_destroy", h)
+            _lib.check(_lib.lib().amp_fvq_create(q0.dim, q0.codebook_dim, q0.codebook_size, len(levels), 1, wi, bi, cb, wo, bo, ctypes.byref(h)))
         return h
 
 

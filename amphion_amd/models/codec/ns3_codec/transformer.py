@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.vocos import _PwHandle, pw_forward
 from amphion_amd.modules.hip_ops import add_channel_bias_, layer_norm_c
@@ -52,26 +53,20 @@ class ConvCache:
 
     def __init__(self, k=1, padding=0, tanh=False):
         self.k, self.padding, self.tanh = k, padding, tanh
-        self._h = self._fin = self._sig = None
-
-    def __deepcopy__(self, memo):
-        return ConvCache(self.k, self.padding, self.tanh)
+        self._cache = HandleCache("amp_conv_destroy")
 
     def _ensure(self, weight, bias, device):
-        sig = (weight.data_ptr(), weight._version, None if bias is None else (bias.data_ptr(), bias._version), str(device), _lib.get_precision())
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w = weight.detach().to("cpu", torch.float32).contiguous()
-        b = bias.detach().to("cpu", torch.float32).contiguous() if bias is not None else None
+        return self._cache.get(param_sig((weight, bias), str(device), _lib.get_precision()), self._build, weight, bias, device)
+
+    def _build(self, weight, bias, device):
+        w, b = host_f32(weight), host_f32(bias)
         cout, cin = w.shape[0], w.shape[1]
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create(0, cin, cout, self.k, 1, 1, self.padding, _p(w), _p(b), ctypes.byref(h)))
+            self._cache.adopt(h)
             if self.tanh:
                 _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_TANH, 1))
-        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
         return h
 
     def __call__(self, weight, bias, x, slope_out=1.0):

@@ -9,8 +9,8 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32_array, param_sig
 from amphion_amd._lib import ptr as _p
-from amphion_amd.models.codec.amphion_codec.codec import _sig
 from amphion_amd.models.codec.amphion_codec.vocos import _check_input, _check_tensors
 
 
@@ -21,29 +21,22 @@ class SLSTM(nn.Module):
         self.skip = skip
         self.dimension = dimension
         self.lstm = nn.LSTM(dimension, dimension, num_layers, bidirectional=bidirectional)
-        self._h, self._hsig, self._fin = None, None, None
+        self._cache = HandleCache("amp_lstm_destroy")
 
     def _handle(self, device):
-        sig = _sig(list(self.lstm.parameters()), device)
-        if self._h is not None and sig == self._hsig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
+        return self._cache.get(param_sig(self.lstm.parameters(), str(device), _lib.get_precision()), self._build, device)
+
+    def _build(self, device):
         lstm = self.lstm
         ndir = 2 if self.bidirectional else 1
-        keep = []
 
         def arr(kind):
-            names = [f"{kind}_l{layer}{'_reverse' if d else ''}" for layer in range(lstm.num_layers) for d in range(ndir)]
-            ts = [getattr(lstm, n).detach().to("cpu", torch.float32).contiguous() for n in names]
-            keep.extend(ts)
-            return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            return host_f32_array([getattr(lstm, f"{kind}_l{layer}{'_reverse' if d else ''}") for layer in range(lstm.num_layers) for d in range(ndir)])
 
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_lstm_create(lstm.input_size, lstm.hidden_size, lstm.num_layers, int(self.bidirectional), int(self.skip),
                                                   arr("weight_ih"), arr("weight_hh"), arr("bias_ih"), arr("bias_hh"), ctypes.byref(h)))
-        self._h, self._hsig, self._fin = h, sig, _lib.finalizer(self, "amp_lstm_destroy", h)
         return h
 
     def run(self, x):

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32_array, param_sig
 from amphion_amd._lib import ptr as _p
 
 
@@ -35,10 +36,7 @@ class EvqHandle:
     """The device copy of a stack of codebooks for ``amp_evq_*``, rebuilt when a codebook or the device changes"""
 
     def __init__(self):
-        self._h, self._sig, self._fin, self._inited = None, None, None, None
-
-    def __deepcopy__(self, memo):
-        return EvqHandle()
+        self._cache, self._inited = HandleCache("amp_evq_destroy"), None
 
     def check_inited(self, codebooks):
         """every codebook must hold trained rows; read once per state of the buffers, not per call: reading a device buffer synchronises"""
@@ -49,21 +47,17 @@ class EvqHandle:
             self._inited = sig
 
     def get(self, codebooks, device):
-        sig = tuple((c.embed.data_ptr(), c.embed._version, c.inited.data_ptr(), c.inited._version) for c in codebooks) + (str(device), len(codebooks))
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        c0 = codebooks[0]
-        K, D = c0.embed.shape
+        sig = param_sig([t for c in codebooks for t in (c.embed, c.inited)], str(device), len(codebooks))
+        return self._cache.get(sig, self._build, codebooks, device)
+
+    def _build(self, codebooks, device):
+        K, D = codebooks[0].embed.shape
         if any(tuple(c.embed.shape) != (K, D) for c in codebooks):
             raise NotImplementedError("ResidualVectorQuantization: levels whose codebooks differ in shape are not on the HIP path")
-        host = [c.embed.detach().to("cpu", torch.float32).contiguous() for c in codebooks]
-        arr = (ctypes.c_void_p * len(host))(*[t.data_ptr() for t in host])
+        arr = host_f32_array([c.embed for c in codebooks])
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().amp_evq_create(D, K, len(host), arr, ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_evq_destroy", h)
+            _lib.check(_lib.lib().amp_evq_create(D, K, len(codebooks), arr, ctypes.byref(h)))
         return h
 
 

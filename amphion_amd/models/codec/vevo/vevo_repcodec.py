@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32_array, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.vocos import _check_input, _check_tensors, _PwHandle, pw_forward
 from amphion_amd.models.codec.kmeans.repcodec_model import no_training
@@ -54,26 +55,19 @@ class _EvqHandle:
     changes"""
 
     def __init__(self):
-        self._h, self._sig, self._fin = None, None, None
-
-    def __deepcopy__(self, memo):
-        return _EvqHandle()
+        self._cache = HandleCache("amp_evq_destroy")
 
     def get(self, layers, device):
-        sig = tuple((q.embed.data_ptr(), q.embed._version) for q in layers) + (str(device), len(layers))
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
+        return self._cache.get(param_sig([q.embed for q in layers], str(device), len(layers)), self._build, layers, device)
+
+    def _build(self, layers, device):
         D, K = layers[0].embed.shape
         if any(tuple(q.embed.shape) != (D, K) for q in layers):
             raise NotImplementedError("ResidualVQ: levels whose codebooks differ in shape are not on the HIP path")
-        host = [q.embed.detach().to("cpu", torch.float32).t().contiguous() for q in layers]
-        arr = (ctypes.c_void_p * len(host))(*[t.data_ptr() for t in host])
+        arr = host_f32_array([q.embed.t() for q in layers])      # [K, dim] rows
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().amp_evq_create(D, K, len(host), arr, ctypes.byref(h)))
-        self._h, self._sig, self._fin = h, sig, _lib.finalizer(self, "amp_evq_destroy", h)
+            _lib.check(_lib.lib().amp_evq_create(D, K, len(layers), arr, ctypes.byref(h)))
         return h
 
 

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 
 
@@ -84,7 +85,7 @@ class DiffWave(nn.Module):
         self.skip_projection = Conv1d(C, C, 1)
         self.output_projection = Conv1d(C, 1, 1)
         nn.init.zeros_(self.output_projection.weight)
-        self._h, self._sig, self._fin = None, None, None
+        self._cache = HandleCache("amp_dw_destroy")
         self._ws = {}
 
     # ---- geometry ----
@@ -104,29 +105,20 @@ class DiffWave(nn.Module):
 
     def handle(self, device):
         """the ``amp_dw`` handle holding this module's weights on ``device`` in the current precision"""
-        prec = _lib.get_precision()
         tensors = list(self.state_dict().items()) + [("diffusion_embedding.embedding", self.diffusion_embedding.embedding)]
-        sig = tuple((t.data_ptr(), t._version) for _, t in tensors) + (str(device), prec)
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-            self._h = None
+        return self._cache.get(param_sig([t for _, t in tensors], str(device), _lib.get_precision()), self._build, tensors, device)
+
+    def _build(self, tensors, device):
         h = ctypes.c_void_p()
         d = self._desc()
         L = _lib.lib()
         with torch.cuda.device(device):
             _lib.check(L.amp_dw_create(ctypes.byref(d), ctypes.byref(h)))
-            fin = _lib.finalizer(self, "amp_dw_destroy", h)
-            try:
-                for k, t in tensors:
-                    w = t.detach().to("cpu", torch.float32).contiguous()
-                    _lib.check(L.amp_dw_set_weight(h, k.encode(), _p(w), w.numel()))
-                _lib.check(L.amp_dw_finalize(h))
-            except Exception:
-                fin()
-                raise
-        self._h, self._sig, self._fin = h, sig, fin
+            self._cache.adopt(h)      # from here on a failure destroys it (HandleCache.build)
+            for k, t in tensors:
+                w = host_f32(t)
+                _lib.check(L.amp_dw_set_weight(h, k.encode(), _p(w), w.numel()))
+            _lib.check(L.amp_dw_finalize(h))
         return h
 
     def workspace(self, B, F, device):

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache
 
 
 # forward_graphed's caches: generator -> {(B, T bucket, device): capture() triple}.  A weak-keyed side table, not attributes: graphs and
@@ -129,12 +130,9 @@ class HipGenerator(nn.Module):
 
     def __init__(self):
         super().__init__()
-        self._amp_handle = None
-        self._amp_finalizer = None
-        self._amp_sig = None
+        self._amp_cache = HandleCache("amp_gen_destroy")     # its signature is (_amp_signature(), device)
         self._amp_snap = None
         self._amp_epoch = 0
-        self._amp_device = None
         self._amp_ws = None
         self._amp_profiling = 0
 
@@ -209,25 +207,34 @@ class HipGenerator(nn.Module):
         """Forget the packed weights: the next forward re-reads every parameter."""
         self._amp_release()
 
+    @property
+    def _amp_handle(self):
+        return self._amp_cache.handle
+
     def _amp_release(self):
-        if self._amp_finalizer is not None:
-            self._amp_finalizer()  # destroys the handle once
-        self._amp_handle = self._amp_finalizer = self._amp_sig = self._amp_device = self._amp_snap = None
+        self._amp_cache.release()
+        self._amp_snap = None
         self._amp_epoch = getattr(self, "_amp_epoch", 0) + 1          # captured graphs of the old handle are dead
 
     def _amp_ensure(self, device):
-        if self._amp_handle is not None and device == self._amp_device and self._amp_unchanged():
-            return self._amp_handle
-        sig = self._amp_signature()
-        if self._amp_handle is not None and sig == self._amp_sig and device == self._amp_device:
+        c = self._amp_cache
+        if c.sig is not None and device == c.sig[1] and self._amp_unchanged():
+            return c.handle
+        sig = (self._amp_signature(), device)
+        if sig == c.sig:
             self._amp_snap = self._amp_snapshot()      # same weights behind re-registered objects
-            return self._amp_handle
+            return c.handle
         self._amp_release()
+        h = c.build(sig, self._amp_build, device)
+        self._amp_snap = self._amp_snapshot()
+        return h
+
+    def _amp_build(self, device):
         L = _lib.lib()
         desc = self._amp_desc()
         h = ctypes.c_void_p()
         _lib.check(L.amp_gen_create(ctypes.byref(desc), ctypes.byref(h)))
-        fin = _lib.finalizer(self, "amp_gen_destroy", h)
+        self._amp_cache.adopt(h)      # from here on a failure destroys it (HandleCache.build)
         prev_prec = L.amp_get_precision()
         try:
             staged = []
@@ -249,13 +256,8 @@ class HipGenerator(nn.Module):
                 _lib.check(L.amp_gen_finalize(h))
                 if self._amp_profiling:
                     _lib.check(L.amp_gen_set_profiling(h, int(self._amp_profiling)))
-        except Exception:
-            fin()
-            raise
         finally:
             L.amp_set_precision(prev_prec)
-        self._amp_handle, self._amp_finalizer, self._amp_sig, self._amp_device = h, fin, sig, device
-        self._amp_snap = self._amp_snapshot()
         return h
 
     def _amp_forward(self, x, g=None, lengths=None, workspace=None, lens_dev=None):

@@ -6,6 +6,7 @@ import ctypes
 import torch
 
 from amphion_amd import _lib
+from amphion_amd._handle import HandleCache, host_f32
 from amphion_amd._lib import ptr as _ptr
 from amphion_amd.models.vocoders.gan.generator._engine import ConvParams
 
@@ -21,9 +22,7 @@ class HipConv1d(ConvParams):
         if pad_mode not in ("zeros", "reflect"):
             raise ValueError(f"pad_mode must be 'zeros' or 'reflect', got {pad_mode!r}")
         self.pad_mode, self.tanh = pad_mode, bool(tanh)
-        self._h = None
-        self._fin = None
-        self._sig = None
+        self._cache, self._gated = HandleCache("amp_conv_destroy"), HandleCache("amp_conv_destroy")
 
     def _param_sig(self):
         """identity + version of every parameter (a leaf module: its own ``_parameters`` only -- ``named_parameters()`` walks the
@@ -31,44 +30,40 @@ class HipConv1d(ConvParams):
         return tuple((n, p.data_ptr(), p._version) for n, p in self._parameters.items() if p is not None)
 
     def _ensure(self, device):
-        sig = self._param_sig() + (device,)
-        if self._h is not None and sig == self._sig:
-            return self._h
-        if self._fin is not None:
-            self._fin()
-        w = self.folded_weight().detach().to("cpu", torch.float32).contiguous()
-        b = self.bias.detach().to("cpu", torch.float32).contiguous() if self.bias is not None else None
+        # keyed on the parameters and the device, NOT on the precision (every other cache is): a handle keeps the arithmetic it was built
+        # with (amphion_hip.h) and ``_prec`` records it.  The look-up is HandleCache.get spelled out: this is the per-launch path
+        c, sig = self._cache, self._param_sig() + (device,)
+        return c.handle if sig == c.sig else c.build(sig, self._build, device)
+
+    def _build(self, device):
+        w, b = host_f32(self.folded_weight()), host_f32(self.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create(int(self.transposed), self.cin, self.cout, self.k, self.stride,
                                                   self.dilation, self.padding, _ptr(w), _ptr(b), ctypes.byref(h)))
+            self._cache.adopt(h)
             if self.pad_mode == "reflect":
                 _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_PAD_REFLECT, 1))
             if self.tanh:
                 _lib.check(_lib.lib().amp_conv_set_option(h, _lib.AMP_CONV_OPT_TANH, 1))
-        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
-        self._prec = _lib.get_precision()      # a handle keeps the arithmetic it was built with (amphion_hip.h)
+        self._prec = _lib.get_precision()
         return h
 
     def _ensure_gated(self, device):
         """A second handle with the 2H rows packed for the gate epilogue of the fused WN layer
         (``amp_conv_create_gated``); None when this conv / arithmetic is outside what that kernel covers."""
-        sig = self._param_sig() + (device, _lib.get_precision())
-        if getattr(self, "_sig_g", None) == sig:
-            return self._hg
-        if getattr(self, "_fin_g", None) is not None:
-            self._fin_g()
-        self._hg, self._fin_g, self._sig_g = None, None, sig
+        c, sig = self._gated, self._param_sig() + (device, _lib.get_precision())
+        return c.handle if sig == c.sig else c.build(sig, self._build_gated, device)
+
+    def _build_gated(self, device):
         if (_lib.get_precision() != "f16x3" or self.transposed or self.cout != 2 * self.cin or self.cin % 32 or self.cin > 256 or self.cout <= 64
                 or self.k not in (1, 3, 5) or self.stride != 1 or 2 * self.padding != self.dilation * (self.k - 1)
                 or (self.k - 1) * self.dilation > 64 or self.pad_mode != "zeros" or self.tanh):
             return None
-        w = self.folded_weight().detach().to("cpu", torch.float32).contiguous()
-        b = self.bias.detach().to("cpu", torch.float32).contiguous() if self.bias is not None else None
+        w, b = host_f32(self.folded_weight()), host_f32(self.bias)
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create_gated(self.cin, self.k, self.dilation, self.padding, _ptr(w), _ptr(b), ctypes.byref(h)))
-        self._hg, self._fin_g = h, _lib.finalizer(self, "amp_conv_destroy", h)
         return h
 
     def forward(self, x, *, slope_in=1.0, res=None, slope_out=1.0, out=None, x_batch_stride=None, T=None, lens=None):
@@ -105,31 +100,24 @@ class MergedConv1d:
     pickle of the owning module starts with an empty cache)."""
 
     def __init__(self):
-        self._h = self._fin = self._sig = None
-
-    def __deepcopy__(self, memo):
-        return MergedConv1d()
-
-    def __reduce__(self):
-        return (MergedConv1d, ())
+        self._cache = HandleCache("amp_conv_destroy")
 
     def _ensure(self, convs, device):
-        sig = tuple(c._param_sig() for c in convs) + (device,)
-        if self._h is not None and sig == self._sig:
-            return self._h
+        # like HipConv1d._ensure: not keyed on the precision, and spelled out for the per-launch path
+        cache, sig = self._cache, tuple(c._param_sig() for c in convs) + (device,)
+        return cache.handle if sig == cache.sig else cache.build(sig, self._build, convs, device)
+
+    def _build(self, convs, device):
         c0 = convs[0]
         if any(c.transposed or (c.cin, c.k, c.stride, c.dilation, c.padding) != (c0.cin, c0.k, c0.stride, c0.dilation, c0.padding)
                or (c.bias is None) != (c0.bias is None) for c in convs):
             raise ValueError("MergedConv1d: the convs must be Conv1d of one geometry")
-        if self._fin is not None:
-            self._fin()
-        w = torch.cat([c.folded_weight().detach().to("cpu", torch.float32) for c in convs], dim=0).contiguous()
-        b = torch.cat([c.bias.detach().to("cpu", torch.float32) for c in convs]).contiguous() if c0.bias is not None else None
+        w = torch.cat([host_f32(c.folded_weight()) for c in convs], dim=0)
+        b = torch.cat([host_f32(c.bias) for c in convs]) if c0.bias is not None else None
         h = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(_lib.lib().amp_conv_create(0, c0.cin, w.shape[0], c0.k, c0.stride, c0.dilation, c0.padding, _ptr(w), _ptr(b),
                                                   ctypes.byref(h)))
-        self._h, self._fin, self._sig = h, _lib.finalizer(self, "amp_conv_destroy", h), sig
         return h
 
     def __call__(self, convs, x, lens=None):
