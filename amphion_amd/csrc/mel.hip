@@ -21,6 +21,14 @@ __device__ __forceinline__ int reflect_index(int s, int L) {
     return s;
 }
 
+// Frames of a ragged row that holds Li samples: amp_mel_num_frames' rule, capped by the batch's F.  A row too short for its reflection padding
+// (Li <= pad) or for one whole frame (Li + 2 pad < n_fft: C division would round the negative quotient up to frame 0) has none.
+__device__ __forceinline__ int ragged_frames(int Li, int pad, int n_fft, int hop, int F) {
+    if (Li <= pad || Li + 2 * pad < n_fft) return 0;
+    const int Fi = (Li + 2 * pad - n_fft) / hop + 1;
+    return Fi < F ? Fi : F;
+}
+
 // utils/mel.py:21-24 wants the extreme samples when the audio leaves [-1, 1].  The front-end kernels fold what they read anyway:
 // `lo` / `hi` = the lane's running min / max; out-of-range lanes (rare) merge into range[0] / range[1] with an atomic max of the
 // int bits -- monotone in the value for floats below -1 (more negative = larger int) and for floats above +1.
@@ -56,9 +64,9 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ wav,
     const int bins = half + 1;
     const float* wb = wav + (size_t)b * L;
     // ragged batch: item b holds lens[b] samples of the zero-padded row; its reflection padding mirrors at ITS
-    // end and it has (lens[b] + 2*pad - n_fft) / hop + 1 frames -- later frames of the row are left untouched
+    // end and it has ragged_frames() frames -- later frames of the row are left untouched
     int Li = L;
-    if (lens) { Li = lens[b] < L ? lens[b] : L; if (f > (Li + 2 * pad - n_fft) / hop || Li <= pad) return; }
+    if (lens) { Li = lens[b] < L ? lens[b] : L; if (f >= ragged_frames(Li, pad, n_fft, hop, F)) return; }
 
     float rlo = 0.f, rhi = 0.f;
     for (int n = tid; n < n_fft; n += 256) {
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(256) void mel_mixed_kernel(const float* __restrict_
     const int bins = (n_fft >> 1) + 1;
     const float* wb = wav + (size_t)b * L;
     int Li = L;
-    if (lens) { Li = lens[b] < L ? lens[b] : L; if (f > (Li + 2 * pad - n_fft) / hop || Li <= pad) return; }
+    if (lens) { Li = lens[b] < L ? lens[b] : L; if (f >= ragged_frames(Li, pad, n_fft, hop, F)) return; }
 
     float rlo = 0.f, rhi = 0.f;
     for (int n = tid; n < n_fft; n += 256) {
@@ -437,12 +445,11 @@ __global__ __launch_bounds__(64 * MEL_WAVES, 4) void mel1024_kernel(const float*
     const int f0 = (blockIdx.x - b * fblocks) * MEL_FPB;
     const float* wb = wav + (size_t)b * L;
     // ragged batch: item b holds lens[b] samples; its reflection padding mirrors at ITS end and it has
-    // (lens[b] + 2*pad - n_fft) / hop + 1 frames -- later frames of the row are left untouched
+    // ragged_frames() frames -- later frames of the row are left untouched
     int Li = L, Fi = F;
     if (lens) {
         Li = lens[b] < L ? lens[b] : L;
-        Fi = Li <= pad ? 0 : (Li + 2 * pad - N) / hop + 1;
-        Fi = Fi < F ? Fi : F;
+        Fi = ragged_frames(Li, pad, N, hop, F);
     }
     if (f0 >= Fi) return;   // workgroup-uniform
 
@@ -829,8 +836,7 @@ __global__ __launch_bounds__(64 * MEL_WAVES, 2) void mel_wave_kernel(const float
     int Li = L, Fi = F;        // ragged batch, see mel1024_kernel
     if (lens) {
         Li = lens[b] < L ? lens[b] : L;
-        Fi = Li <= pad ? 0 : (Li + 2 * pad - N) / hop + 1;
-        Fi = Fi < F ? Fi : F;
+        Fi = ragged_frames(Li, pad, N, hop, F);
     }
     if (f0 >= Fi) return;   // workgroup-uniform
 
@@ -1498,8 +1504,7 @@ __global__ __launch_bounds__(256) void mel_grad_ola_kernel(const float* __restri
     int Li = L, Fi = F;
     if (lens) {
         Li = lens[b] < L ? lens[b] : L;
-        Fi = Li <= pad ? 0 : (Li + 2 * pad - n_fft) / hop + 1;
-        Fi = Fi < F ? Fi : F;
+        Fi = ragged_frames(Li, pad, n_fft, hop, F);
     }
     float acc = 0.f;
     if (s < Li) {

@@ -250,20 +250,27 @@ def _run(y, cfg, *, n_mel, pad_mode, mag_eps, log_clip, want=("mel",), basis=Non
 
 
 def num_frames(n_samples, cfg):
-    """Frames ``extract_mel_features`` yields for ``n_samples`` (reflect pad (n_fft-hop)/2, center=False)."""
+    """Frames ``extract_mel_features`` yields for ``n_samples`` (reflect pad (n_fft-hop)/2, center=False); 0 when the padded
+    signal is shorter than one frame (``amp_mel_num_frames``' rule)."""
     pad = (cfg.n_fft - cfg.hop_size) // 2
-    return (n_samples + 2 * pad - cfg.n_fft) // cfg.hop_size + 1
+    return max(0, (n_samples + 2 * pad - cfg.n_fft) // cfg.hop_size + 1)
 
 
 def extract_mel_features_batch(wavs, cfg, device=None):
     """``extract_mel_features`` (utils/mel.py:111-170) over a LIST of waveforms of different lengths in ONE kernel
     launch: the batch is zero-padded, every utterance is reflect-padded at its own end
     (``amp_mel_forward_ragged``), and each returned ``[n_mel, F_i]`` equals the one-file-at-a-time result of the
-    reference's feature extraction (processors/acoustic_extractor.py:394-401)."""
+    reference's feature extraction (processors/acoustic_extractor.py:394-401).  An utterance too short for its reflection
+    padding or for one frame raises ``ValueError`` (the one-file-at-a-time extraction raises there too)."""
     if len(wavs) == 0:
         return []
-    device = device or (wavs[0].device if isinstance(wavs[0], torch.Tensor) and wavs[0].is_cuda else "cuda")
     lens = [int(w.shape[-1]) for w in wavs]
+    pad = (cfg.n_fft - cfg.hop_size) // 2
+    for i, n in enumerate(lens):
+        if n <= pad or num_frames(n, cfg) <= 0:
+            raise ValueError(f"utterance {i} of the batch yields no frame: {n} samples (reflect padding {pad}, n_fft {cfg.n_fft}, "
+                             f"hop {cfg.hop_size})")
+    device = device or (wavs[0].device if isinstance(wavs[0], torch.Tensor) and wavs[0].is_cuda else "cuda")
     batch = torch.zeros((len(wavs), max(lens)), dtype=torch.float32)
     for i, w in enumerate(wavs):
         batch[i, : lens[i]] = torch.as_tensor(w, dtype=torch.float32).reshape(-1).cpu()

@@ -555,7 +555,10 @@ int amp_mel_forward(const amp_mel_desc* d, const float* wav_dev, int B, int L, c
 /* Ragged batch of the same: row b of wav_dev [B, L] holds lens_dev[b] <= L samples (int32, device), zero-padded.
  * Every utterance is reflect-padded at ITS OWN end and fills frames [0, amp_mel_num_frames(d, lens[b])) of its
  * output rows -- identical to running it alone (what the reference's one-file-at-a-time feature extraction,
- * processors/acoustic_extractor.py:376-403, computes); later frames of a row are left unwritten. */
+ * processors/acoustic_extractor.py:376-403, computes); later frames of a row are left unwritten.
+ * ZERO-FRAME ROWS: a row with lens[b] <= the reflection padding, or with lens[b] + 2 * padding < n_fft (possible with
+ * pad_mode 0 whenever hop > n_fft / 3: padding < lens[b] < hop), has amp_mel_num_frames(d, lens[b]) == 0 frames: none of
+ * its samples is read and none of its output rows is written. */
 int amp_mel_forward_ragged(const amp_mel_desc* d, const float* wav_dev, const int32_t* lens_dev, int B, int L,
                            const float* window_dev, const float* melbasis_dev, float* mel_dev, float* mag_dev,
                            float* re_dev, float* im_dev, void* stream);
@@ -566,7 +569,8 @@ int amp_mel_forward_ragged(const amp_mel_desc* d, const float* wav_dev, const in
  * mag_dev / re_dev / im_dev [B, n_fft/2+1, F] -- plus grad_logmel_dev [B, n_mel, F] = d loss / d log(max(mel,
  * d->log_clip)) (d->log_clip <= 0: the gradient w.r.t. the linear mel).  Output grad_wav_dev [B, L].
  * spec_ws_dev: scratch of 2 * B * (n_fft/2+1) * F floats, frames_ws_dev: B * F * n_fft floats.  lens_dev as in
- * amp_mel_forward_ragged (NULL = full rows). */
+ * amp_mel_forward_ragged (NULL = full rows): row b reads frames [0, amp_mel_num_frames(d, lens[b])) of its inputs only,
+ * its gradient is 0 from column lens[b] on, and a zero-frame row (see amp_mel_forward_ragged) gets an all-zero gradient. */
 int amp_mel_backward(const amp_mel_desc* d, const int32_t* lens_dev, int B, int L, const float* window_dev,
                      const float* melbasis_dev, const float* mel_linear_dev, const float* mag_dev, const float* re_dev,
                      const float* im_dev, const float* grad_logmel_dev, float* spec_ws_dev, float* frames_ws_dev,

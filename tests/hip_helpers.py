@@ -349,3 +349,81 @@ def aa_unit_forward(alpha1, beta1, w1, b1, alpha2, beta2, w2, b2, fu, fd, xs, *,
         return out if many else out[0]
     finally:
         L.amp_aa_unit_destroy(h)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the mel / STFT entry points with raw pointers (tests/test_gpu_stft_geometry.py).  These return the status instead of raising, so a refusal can
+# be looked at; `Fenced` is `Guarded` with a choice of fill (a finite sentinel where NaN is a legitimate input) and of alignment.
+# ------------------------------------------------------------------------------------------------------------------------------
+class Fenced:
+    """a device tensor of `shape`, `offset` floats off a 16-byte boundary, filled with `fill` and between two runs of SENTINEL floats of it"""
+
+    def __init__(self, shape, offset=0, fill=float("nan")):
+        self.n = 1
+        for v in shape:
+            self.n *= int(v)
+        self.fill = fill
+        self.lo = SENTINEL + offset
+        self.buf = torch.full((self.n + 2 * SENTINEL + offset,), fill, device="cuda")
+        self.t = self.buf[self.lo:self.lo + self.n].view(*shape)
+        assert self.t.data_ptr() % 16 == 4 * (offset % 4)
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.t.data_ptr())
+
+    def untouched(self, part):
+        return torch.isnan(part) if self.fill != self.fill else part == self.fill
+
+    def check_fences(self, what):
+        torch.cuda.synchronize()
+        for name, part in (("in front of", self.buf[:self.lo]), ("behind", self.buf[self.lo + self.n:])):
+            hit = (~self.untouched(part)).nonzero().flatten().tolist()
+            assert not hit, f"{what}: the sentinel floats {hit[:8]} {name} the tensor were written"
+
+    def check_written(self, what):
+        self.check_fences(what)
+        bad = (~torch.isfinite(self.t) | self.untouched(self.t)).nonzero()
+        assert bad.numel() == 0, f"{what}: {bad.shape[0]} of {self.n} elements were not written or are not finite; first at {bad[:4].tolist()}"
+        return self.t
+
+
+def mel_desc(n_fft, win, hop, n_mel=0, pad_mode=0, mag_eps=0.0, log_clip=0.0):
+    return _lib.amp_mel_desc(n_fft, win, hop, n_mel, pad_mode, mag_eps, log_clip, None)
+
+
+def _raw(t):
+    """c_void_p of a tensor, a Fenced, or None"""
+    if t is None:
+        return None
+    return t.ptr if isinstance(t, Fenced) else ctypes.c_void_p(t.data_ptr())
+
+
+def _st():
+    return _lib.current_stream_ptr(torch.device("cuda:0"))
+
+
+def last_error():
+    return _lib.lib().amp_last_error().decode("utf-8", "replace")
+
+
+def istft_call(mode, d, a, b, B, F, window, den, frames, wav, stride=0, clip=0.0):
+    """amp_istft_forward (a, b = mag, phase) / amp_istft_same (re, im) / amp_istft_same_polar (a = head) -> status"""
+    L = _lib.lib()
+    if mode == "forward":
+        return L.amp_istft_forward(ctypes.byref(d), _raw(a), _raw(b), B, F, _raw(window), _raw(den), _raw(frames), _raw(wav), _st())
+    if mode == "same":
+        return L.amp_istft_same(ctypes.byref(d), _raw(a), _raw(b), B, F, _raw(window), _raw(den), _raw(frames), _raw(wav), _st())
+    return L.amp_istft_same_polar(ctypes.byref(d), _raw(a), int(stride), B, F, float(clip), _raw(window), _raw(den), _raw(frames), _raw(wav), _st())
+
+
+def mel_forward_call(d, wav, lens, B, Ln, window, basis, mel, mag, re, im):
+    """amp_mel_forward_ragged (lens None: full rows) -> status"""
+    return _lib.lib().amp_mel_forward_ragged(ctypes.byref(d), _raw(wav), _raw(lens), B, Ln, _raw(window), _raw(basis), _raw(mel), _raw(mag),
+                                             _raw(re), _raw(im), _st())
+
+
+def mel_backward_call(d, lens, B, Ln, window, basis, mel_lin, mag, re, im, g, spec_ws, frames_ws, gw):
+    """amp_mel_backward -> status"""
+    return _lib.lib().amp_mel_backward(ctypes.byref(d), _raw(lens), B, Ln, _raw(window), _raw(basis), _raw(mel_lin), _raw(mag), _raw(re),
+                                       _raw(im), _raw(g), _raw(spec_ws), _raw(frames_ws), _raw(gw), _st())

@@ -191,6 +191,31 @@ def test_mel_num_frames():
     assert L.amp_mel_num_frames(ctypes.byref(d), 256 * 40) == 41    # TacotronSTFT: L/hop + 1
 
 
+def test_mel_num_frames_clamps_and_the_batch_refuses_zero_frame_utterances():
+    """An utterance with ``len <= pad`` or ``len + 2 pad < n_fft`` has no frame: ``num_frames`` says 0 (floor division gave -1 and
+    below), in step with ``amp_mel_num_frames`` at every length, and ``extract_mel_features_batch`` raises naming the utterance
+    before it touches a device (this test has none)."""
+    from amphion_amd.utils import mel as M
+
+    L = _lib.lib()
+    for n_fft, hop in ((400, 160), (512, 256), (1000, 400), (1001, 501), (646, 320), (1024, 256)):
+        pp = NS(sample_rate=16000, n_fft=n_fft, win_size=n_fft, hop_size=hop, n_mel=8, fmin=0, fmax=None)
+        d = _lib.amp_mel_desc(n_fft, n_fft, hop, 8, 0, 1e-9, 1e-5)
+        for n in range(0, 2 * n_fft + 3):
+            assert M.num_frames(n, pp) == L.amp_mel_num_frames(ctypes.byref(d), n) >= 0, (n_fft, hop, n)
+        pad = (n_fft - hop) // 2
+        assert M.num_frames(hop - 1, pp) == 0 and M.num_frames(0, pp) == 0 and M.num_frames(hop + 1, pp) == 1
+        ok = torch.zeros(4 * n_fft)
+        for short, where in ((pad, 2), (1, 0), (pad + 1, 1), (hop - 1, 1)):
+            if M.num_frames(short, pp) > 0 and short > pad:
+                continue                                           # hop <= n_fft / 3: one sample past the padding already has a frame
+            wavs = [ok, ok, ok]
+            wavs[where] = torch.zeros(short)
+            with pytest.raises(ValueError, match=rf"utterance {where} "):
+                M.extract_mel_features_batch(wavs, pp, device="cuda")
+    assert M.extract_mel_features_batch([], NS(n_fft=1024, hop_size=256)) == []
+
+
 def _model(seed=1234):
     from amphion_amd.models.vocoders.gan.generator.hifigan import HiFiGAN
 
