@@ -194,6 +194,86 @@ __global__ __launch_bounds__(256) void layer_norm_c_kernel(const float* __restri
     for (int c = g + LN_G * NC; c < C; c += LN_G) emit(c, value(c));
 }
 
+// The style-adaptive LayerNorm of FACodec's conditioned transformer (models/codec/ns3_codec/transformer.py:13-32) and the
+// `timbre_norm(x) * gamma + beta` of its decoders: y[b, c, t] = style[b, c] * LN_c(x + res)[b, c, t] + style[b, C + c], the scale and
+// shift one row of `style` [B, 2C] PER ITEM where layer_norm_c_kernel<0, NC> takes one vector for the batch.  The same workgroup shape,
+// register file, two reductions and ln_affine: with style[b] = (gamma | beta) for every b it gives the bits of that kernel.  x is read
+// once (C <= 8 NC; beyond that the plain re-reading form, as there) and y written once.
+template <int NC>
+__global__ __launch_bounds__(256) void layer_norm_c_style_kernel(const float* __restrict__ x, const float* __restrict__ res,
+                                                                 const float* __restrict__ style, float* __restrict__ y, int C, int T,
+                                                                 float eps) {
+    __shared__ float red[LN_G][LN_TT + 1];
+    const int tx = threadIdx.x & (LN_TT - 1), g = threadIdx.x / LN_TT;
+    const int t = blockIdx.x * LN_TT + tx;
+    const int b = blockIdx.y;
+    const bool ok = t < T;
+    const size_t base = (size_t)b * C * T + (ok ? t : 0);
+    const float* xb = x + base;
+    const float* rb = res ? res + base : nullptr;
+    const float* gam = style + (size_t)b * 2 * C;
+    const float* bet = gam + C;
+    auto value = [&](int c) { return xb[(size_t)c * T] + (rb ? rb[(size_t)c * T] : 0.f); };
+    auto reduce = [&](float part) {                      // layer_norm_c_kernel's: the 8 channel groups of column tx in a fixed order
+        red[g][tx] = part;
+        __syncthreads();
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < LN_G; ++k) s += red[k][tx];
+        __syncthreads();
+        return s;
+    };
+    float v[NC];
+    float part = 0.f;
+    {
+        float xr[NC], rr[NC];                            // every load unconditional and issued before the first use (clamped index)
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c = g + LN_G * i;
+            xr[i] = xb[(size_t)(c < C ? c : C - 1) * T];
+        }
+        if (rb) {                                        // block-uniform
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const int c = g + LN_G * i;
+                rr[i] = rb[(size_t)(c < C ? c : C - 1) * T];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) rr[i] = 0.f;
+        }
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            v[i] = (ok && g + LN_G * i < C) ? xr[i] + rr[i] : 0.f;
+            part += v[i];
+        }
+    }
+    for (int c = g + LN_G * NC; c < C; c += LN_G) part += ok ? value(c) : 0.f;
+    float gr[NC], br[NC];                                // the item's scale and shift, requested behind the two reductions
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int c = g + LN_G * i;
+        const int cc = c < C ? c : C - 1;
+        gr[i] = gam[cc];
+        br[i] = bet[cc];
+    }
+    const float mu = reduce(part) / (float)C;
+    part = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) part = ln_sq_acc(part, v[i] - mu, g + LN_G * i < C);
+    for (int c = g + LN_G * NC; c < C; c += LN_G) part = ln_sq_acc(part, (ok ? value(c) : 0.f) - mu, true);
+    const float rstd = 1.0f / sqrtf(reduce(part) / (float)C + eps);
+    if (!ok) return;
+    float* yb = y + base;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int c = g + LN_G * i;
+        if (c < C) yb[(size_t)c * T] = ln_affine(v[i], mu, rstd, gr[i], br[i]);
+    }
+    for (int c = g + LN_G * NC; c < C; c += LN_G) yb[(size_t)c * T] = ln_affine(value(c), mu, rstd, gam[c], bet[c]);
+}
+
 // The seam between two DDSConv layers (modules/flow/modules.py:63-70) in ONE launch instead of two LayerNorm launches:
 //     x_new = x + gelu(LN_2(y))                        (layer i:   norms_2[i] on the 1 x 1 conv's output, residual)
 //     z     = gelu(LN_1'(dwconv'(x_new * mask)))        (layer i+1: convs_sep[i+1] -> norms_1[i+1])
@@ -824,6 +904,61 @@ __global__ __launch_bounds__(256) void embed_kernel(const long long* __restrict_
     y[(size_t)bh * T + t] = w[(size_t)id * Hd + hh] * scale * mk;
 }
 
+// The code-embedding sums of FACodec's redecoder (models/codec/ns3_codec/facodec.py:698-722,736-759): N tables W_n [rows_n, D], codes
+// int64 [N, B, T] -> y[b, :, t] = ((init[b, :, t] + W_0[c_0]) + W_1[c_1]) + ..., channel-first.  Table rows are contiguous along D, y and init
+// along T: a workgroup owns 32 frames x 64 channels and transposes through LDS, so the gathers read 256-B row segments and the init loads
+// and y stores 128-B time segments.  fp32 adds, left to right; with init = NULL the sum starts from the row of W_0 itself.  An index outside
+// [0, rows_n) raises the flag and reads row 0 instead.
+constexpr int ES_TT = 32, ES_DT = 64, ES_MAXN = 8;
+struct EmbedSumArgs {
+    const long long* codes;              // [N, B, T]
+    const float* table[ES_MAXN];
+    int rows[ES_MAXN];
+    const float* init;                   // [B, D, T] or NULL
+    float* y;                            // [B, D, T]
+    unsigned* flag;
+    int N, B, D, T;
+};
+__global__ __launch_bounds__(256) void embed_sum_c_kernel(const EmbedSumArgs a) {
+    __shared__ float tile[ES_TT][ES_DT + 1];
+    __shared__ int code[ES_MAXN][ES_TT];
+    const int tid = threadIdx.x;
+    const int t0 = blockIdx.x * ES_TT, d0 = blockIdx.y * ES_DT, b = blockIdx.z;
+    const int D = a.D, T = a.T;
+    {                                                            // ES_MAXN x ES_TT = 256: one (table, frame) per thread
+        const int n = tid / ES_TT, f = tid & (ES_TT - 1);
+        int rows = 0;                                            // (static indices only: the argument struct stays in the kernarg segment)
+#pragma unroll
+        for (int k = 0; k < ES_MAXN; ++k) rows = k == n ? a.rows[k] : rows;
+        if (n < a.N) {
+            long long c = t0 + f < T ? a.codes[((size_t)n * a.B + b) * T + t0 + f] : 0;
+            if (c < 0 || c >= rows) { atomicOr(a.flag, 1u); c = 0; }
+            code[n][f] = (int)c;
+        }
+    }
+    const int tx = tid & (ES_TT - 1), dy = tid / ES_TT;          // the time-major side: frame tx, channels dy, dy + 8, ..
+    const size_t obase = ((size_t)b * D + d0) * T + t0 + tx;
+    if (a.init && t0 + tx < T) {                                 // (a.init is block-uniform)
+        for (int d = dy; d < ES_DT && d0 + d < D; d += 256 / ES_TT) tile[tx][d] = a.init[obase + (size_t)d * T];
+    }
+    __syncthreads();
+    const int dx = tid & (ES_DT - 1), fy = tid / ES_DT;          // the row-major side: channel dx, frames fy, fy + 4, ..
+    if (d0 + dx < D) {
+        for (int f = fy; f < ES_TT && t0 + f < T; f += 256 / ES_DT) {
+            float acc = a.table[0][(size_t)code[0][f] * D + d0 + dx];
+            if (a.init) acc = tile[f][dx] + acc;
+#pragma unroll
+            for (int n = 1; n < ES_MAXN; ++n)
+                if (n < a.N) acc += a.table[n][(size_t)code[n][f] * D + d0 + dx];
+            tile[f][dx] = acc;
+        }
+    }
+    __syncthreads();
+    if (t0 + tx < T) {
+        for (int d = dy; d < ES_DT && d0 + d < D; d += 256 / ES_TT) a.y[obase + (size_t)d * T] = tile[tx][d];
+    }
+}
+
 // Durations: w_ceil = ceil(exp(logw) * mask * length_scale), its running sum and y_len = max(sum, 1)
 // (SynthesizerTrn.infer vits.py:341-343; the cumsum of generate_path utils/util.py:633).  One thread per item:
 // T_text is ~10^2 and the sum must be sequential anyway.
@@ -959,6 +1094,15 @@ int amp_layer_norm_c_ragged(const float* x_dev, const float* res_dev, const floa
                             void* stream) {
     return layer_norm_run("amp_layer_norm_c_ragged", x_dev, res_dev, gamma_dev, beta_dev, post_dev, lens_dev, nullptr, nullptr, 0, 1, B,
                           C, T, eps, gelu, y_dev, stream);
+}
+
+int amp_layer_norm_c_style(const float* x_dev, const float* res_dev, const float* style_dev, int B, int C, int T, float eps, float* y_dev,
+                           void* stream) {
+    VT_CHECK(x_dev && style_dev && y_dev && B > 0 && C > 0 && T > 0 && B <= 65535, "amp_layer_norm_c_style: bad argument");
+    auto kern = C <= 24 * LN_G ? layer_norm_c_style_kernel<24> : layer_norm_c_style_kernel<32>;
+    hipLaunchKernelGGL(kern, dim3((T + LN_TT - 1) / LN_TT, B), dim3(256), 0, (hipStream_t)stream, x_dev, res_dev, style_dev, y_dev, C, T, eps);
+    VT_LAUNCHED("amp_layer_norm_c_style");
+    return AMP_OK;
 }
 
 int amp_dds_seam(const float* y_dev, const float* x_dev, const float* gamma2_dev, const float* beta2_dev, float eps2,
@@ -1106,6 +1250,41 @@ int amp_embed_tokens(const long long* tokens_dev, const float* weight_dev, const
     hipLaunchKernelGGL(embed_kernel, dim3((T + 255) / 256, B * hidden), dim3(256), 0, (hipStream_t)stream, tokens_dev, weight_dev,
                        lens_dev, y_dev, hidden, T, n_vocab, scale);
     VT_LAUNCHED("amp_embed_tokens");
+    return AMP_OK;
+}
+
+int amp_embed_sum_c(const long long* codes_dev, int N, const float* const* tables, const int* rows, int D, const float* init_dev, int B, int T,
+                    float* y_dev, unsigned* flag_dev, void* stream) {
+    VT_CHECK(codes_dev && tables && rows && y_dev && flag_dev && B > 0 && T > 0 && D > 0, "amp_embed_sum_c: bad argument");
+    VT_CHECK(N >= 1 && N <= ES_MAXN, "amp_embed_sum_c: %d tables (1..%d)", N, ES_MAXN);
+    VT_CHECK(init_dev != y_dev, "amp_embed_sum_c: y must not alias init (a workgroup reads init beside another's stores)");
+    EmbedSumArgs a{};
+    for (int n = 0; n < N; ++n) {
+        VT_CHECK(tables[n] && rows[n] > 0, "amp_embed_sum_c: table %d is null or empty", n);
+        a.table[n] = tables[n];
+        a.rows[n] = rows[n];
+    }
+    const int gd = (D + ES_DT - 1) / ES_DT;
+    if (B > 65535 || gd > 65535) { set_error("amp_embed_sum_c: B=%d D=%d is beyond the grid", B, D); return AMP_ERR_UNSUPPORTED; }
+    a.codes = codes_dev; a.init = init_dev; a.y = y_dev; a.flag = flag_dev;
+    a.N = N; a.B = B; a.D = D; a.T = T;
+    hipLaunchKernelGGL(embed_sum_c_kernel, dim3((T + ES_TT - 1) / ES_TT, gd, B), dim3(256), 0, (hipStream_t)stream, a);
+    VT_LAUNCHED("amp_embed_sum_c");
+    return AMP_OK;
+}
+
+int amp_embed_sum_check(unsigned* flag_dev, void* stream) {
+    VT_CHECK(flag_dev, "amp_embed_sum_check: null flag");
+    unsigned v = 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(&v, flag_dev, sizeof(v), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && v) {
+        e = hipMemsetAsync(flag_dev, 0, sizeof(v), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) { set_error("amp_embed_sum_check: %s", hipGetErrorString(e)); return AMP_ERR_HIP; }
+    VT_CHECK(!v, "amp_embed_sum_c: a code index outside its table was given since the last check (the output of that call used row 0 in its place)");
     return AMP_OK;
 }
 

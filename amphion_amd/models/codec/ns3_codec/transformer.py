@@ -1,5 +1,6 @@
-"""The timbre encoder of FACodec (models/codec/ns3_codec/transformer.py:35-234): 4 pre-LN transformer layers (hidden 256, 4 heads, FFN
-Conv1d(256, 1024, 5) -> ReLU -> Linear), eval mode, ``use_cln=False``.  Same class names, constructor arguments and ``state_dict`` keys
+"""The transformer encoder of FACodec (models/codec/ns3_codec/transformer.py:13-234): 4 pre-LN transformer layers (hidden 256, 4 heads, FFN
+Conv1d(256, 1024, 5) -> ReLU -> Linear), eval mode, plain (``use_cln=False``: the timbre and mel-spectrogram encoders) or conditioned on a
+speaker embedding (``use_cln=True``: the redecoder's prosody encoder).  Same class names, constructor arguments and ``state_dict`` keys
 (``nn.LayerNorm`` / ``nn.MultiheadAttention`` / ``nn.Conv1d`` / ``nn.Linear`` hold the parameters; their forwards are not used).
 
 It runs once per utterance at the frame rate and is composed channel-first ([B, 256, T]) from existing launches: the channel LayerNorm
@@ -12,7 +13,12 @@ for an embedding that is compared at 1e-6.)
 
 The position-embedding quirk of the reference is kept: ``PositionalEncoding.forward`` adds ``pe[: x.size(0)]`` to a BATCH-FIRST tensor
 (transformer.py:50, called with [B, T, d]), so row ``pe[b]`` is added to EVERY frame of item b -- the result depends on the item's index in the
-batch, not on time.  ``use_cln=True`` (StyleAdaptiveLayerNorm) is not on the HIP path."""
+batch, not on time.
+
+``use_cln=True``: ``ln_1`` / ``ln_2`` / ``last_ln`` are ``StyleAdaptiveLayerNorm``.  The condition [B, T, d] is averaged over time once per
+forward (every norm takes the same mean, transformer.py:25), each norm's ``style`` Linear runs on that [B, d, 1] column through the pointwise
+GEMM, and its [B, 2 d] result is the per-item scale | shift of ONE ``amp_layer_norm_c_style`` launch: two launches per norm, nine norms per
+forward.  A padding mask is refused in both forms."""
 from __future__ import annotations
 
 import ctypes
@@ -26,7 +32,7 @@ from amphion_amd import _lib
 from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _p
 from amphion_amd.models.codec.amphion_codec.vocos import _PwHandle, pw_forward
-from amphion_amd.modules.hip_ops import add_channel_bias_, layer_norm_c
+from amphion_amd.modules.hip_ops import add_channel_bias_, layer_norm_c, layer_norm_c_style
 
 AMP_PW_BIAS, AMP_PW_SCALE_RES = 0, 2      # include/amphion_hip.h: amp_pw_epilogue
 
@@ -80,6 +86,39 @@ class ConvCache:
         return out
 
 
+class StyleAdaptiveLayerNorm(nn.Module):
+    """transformer.py:13-32: ``style`` is the only parameter holder (``norm`` has no affine)"""
+
+    def __init__(self, normalized_shape, eps=1e-5):
+        super().__init__()
+        self.in_dim = normalized_shape
+        self.norm = nn.LayerNorm(self.in_dim, eps=eps, elementwise_affine=False)
+        self.style = nn.Linear(self.in_dim, self.in_dim * 2)
+        self.style.bias.data[: self.in_dim] = 1
+        self.style.bias.data[self.in_dim:] = 0
+        self._h = _PwHandle()
+
+    def forward_cf(self, x, cond_mean):
+        """x [B, d, T] channel-first, cond_mean [B, d, 1] (the condition's mean over time) -> gamma * LN(x) + beta"""
+        return layer_norm_c_style(x, pw(self._h, self.style, cond_mean), eps=self.norm.eps)
+
+    def forward(self, x, condition):
+        """x [B, T, d], condition [B, T, d], as the reference takes them"""
+        x = _lib.require_device_tensor(x, "StyleAdaptiveLayerNorm input")
+        condition = _lib.require_device_tensor(condition, "StyleAdaptiveLayerNorm condition")
+        if x.dim() != 3 or x.shape[2] != self.in_dim or condition.dim() != 3 or condition.shape[2] != self.in_dim or condition.shape[0] != x.shape[0]:
+            raise ValueError(f"StyleAdaptiveLayerNorm: expected x and condition [B, T, {self.in_dim}], got {tuple(x.shape)} and {tuple(condition.shape)}")
+        with _lib.on_device(x.device):
+            m = torch.mean(condition, dim=1, keepdim=True).transpose(1, 2).contiguous()
+            return self.forward_cf(x.transpose(1, 2).contiguous(), m).transpose(1, 2)
+
+
+def _norm(ln, x, cond_mean):
+    if cond_mean is None:
+        return layer_norm_c(x, ln.weight.detach(), ln.bias.detach(), eps=ln.eps)
+    return ln.forward_cf(x, cond_mean)
+
+
 class PositionalEncoding(nn.Module):
     def __init__(self, d_model, dropout, max_len=5000):
         super().__init__()
@@ -123,30 +162,29 @@ class TransformerFFNLayer(nn.Module):
 class TransformerEncoderLayer(nn.Module):
     def __init__(self, encoder_hidden, encoder_head, conv_filter_size, conv_kernel_size, encoder_dropout, use_cln):
         super().__init__()
-        if use_cln:
-            raise NotImplementedError("TransformerEncoderLayer: use_cln=True (StyleAdaptiveLayerNorm) is not on the HIP path")
         self.encoder_hidden = encoder_hidden
         self.encoder_head = encoder_head
         self.conv_filter_size = conv_filter_size
         self.conv_kernel_size = conv_kernel_size
         self.encoder_dropout = encoder_dropout
         self.use_cln = use_cln
-        self.ln_1 = nn.LayerNorm(encoder_hidden)
-        self.ln_2 = nn.LayerNorm(encoder_hidden)
+        norm = StyleAdaptiveLayerNorm if use_cln else nn.LayerNorm
+        self.ln_1 = norm(encoder_hidden)
+        self.ln_2 = norm(encoder_hidden)
         self.self_attn = nn.MultiheadAttention(encoder_hidden, encoder_head, batch_first=True)
         self.ffn = TransformerFFNLayer(encoder_hidden, conv_filter_size, conv_kernel_size, encoder_dropout)
         self._qkv, self._out = _PwHandle(), _PwHandle()
 
-    def forward_cf(self, x):
+    def forward_cf(self, x, cond_mean=None):
         B, H, T = x.shape
         nh = self.encoder_head
         a = self.self_attn
-        h = layer_norm_c(x, self.ln_1.weight.detach(), self.ln_1.bias.detach(), eps=self.ln_1.eps)
+        h = _norm(self.ln_1, x, cond_mean)
         qkv = pw(self._qkv, _LinearView(a.in_proj_weight, a.in_proj_bias), h)
         q, k, v = (t.reshape(B, nh, H // nh, T).transpose(2, 3) for t in qkv.chunk(3, 1))
         att = F.scaled_dot_product_attention(q, k, v).transpose(2, 3).reshape(B, H, T).contiguous()
         x = pw(self._out, a.out_proj, att, res=x)
-        h = layer_norm_c(x, self.ln_2.weight.detach(), self.ln_2.bias.detach(), eps=self.ln_2.eps)
+        h = _norm(self.ln_2, x, cond_mean)
         return self.ffn.forward_cf(h, x)
 
 
@@ -161,31 +199,54 @@ class TransformerEncoder(nn.Module):
         self.conv_kernel_size = conv_kernel_size if conv_kernel_size is not None else cfg.conv_kernel_size
         self.encoder_dropout = encoder_dropout if encoder_dropout is not None else cfg.encoder_dropout
         self.use_cln = use_cln if use_cln is not None else cfg.use_cln
-        if self.use_cln:
-            raise NotImplementedError("TransformerEncoder: use_cln=True (StyleAdaptiveLayerNorm) is not on the HIP path")
         if enc_emb_tokens is not None:
             raise NotImplementedError("TransformerEncoder: token embeddings are not on the HIP path (FACodec passes features)")
         self.use_enc_emb = False
         self.position_emb = PositionalEncoding(self.encoder_hidden, self.encoder_dropout)
         self.layers = nn.ModuleList([TransformerEncoderLayer(self.encoder_hidden, self.encoder_head, self.conv_filter_size, self.conv_kernel_size,
                                                              self.encoder_dropout, self.use_cln) for _ in range(self.encoder_layer)])
-        self.last_ln = nn.LayerNorm(self.encoder_hidden)
+        self.last_ln = StyleAdaptiveLayerNorm(self.encoder_hidden) if self.use_cln else nn.LayerNorm(self.encoder_hidden)
 
-    def forward_cf(self, x):
-        """x [B, hidden, T] channel-first -> [B, hidden, T]"""
+    def forward_cf(self, x, cond_mean=None):
+        """x [B, hidden, T] channel-first -> [B, hidden, T]; ``use_cln=True``: cond_mean [B, hidden] or [B, hidden, 1], the condition's mean
+        over time"""
         if self.training:
             raise NotImplementedError("TransformerEncoder: training mode (dropout) is not on the HIP path: call .eval()")
         x = _lib.require_device_tensor(x, "TransformerEncoder input")
         if x.dim() != 3 or x.shape[1] != self.encoder_hidden or x.shape[0] < 1 or x.shape[2] < 1:
             raise ValueError(f"TransformerEncoder: expected a non-empty [B, {self.encoder_hidden}, T] input, got {tuple(x.shape)}")
+        if self.use_cln:
+            if cond_mean is None:
+                raise ValueError("TransformerEncoder: use_cln=True needs a condition")
+            cond_mean = _lib.require_device_tensor(cond_mean, "TransformerEncoder condition")
+            if cond_mean.numel() != x.shape[0] * self.encoder_hidden or cond_mean.shape[0] != x.shape[0] or cond_mean.device != x.device:
+                raise ValueError(f"TransformerEncoder: expected a condition mean {(x.shape[0], self.encoder_hidden)} on {x.device}, got "
+                                 f"{tuple(cond_mean.shape)} on {cond_mean.device}")
+            cond_mean = cond_mean.reshape(x.shape[0], self.encoder_hidden, 1)
+        elif cond_mean is not None:
+            raise ValueError("TransformerEncoder: a condition needs use_cln=True (the reference ignores it; passing one is a mistake)")
         with _lib.on_device(x.device):
             x = self.position_emb.forward_cf(x)
             for layer in self.layers:
-                x = layer.forward_cf(x)
-            return layer_norm_c(x, self.last_ln.weight.detach(), self.last_ln.bias.detach(), eps=self.last_ln.eps)
+                x = layer.forward_cf(x, cond_mean)
+            return _norm(self.last_ln, x, cond_mean)
 
     def forward(self, x, key_padding_mask=None, condition=None):
         """x [B, T, hidden] batch-first, as the reference takes it -> [B, T, hidden]"""
-        if key_padding_mask is not None or condition is not None:
-            raise NotImplementedError("TransformerEncoder: a padding mask / condition is not on the HIP path (FACodec passes None)")
-        return self.forward_cf(x.transpose(1, 2).contiguous()).transpose(1, 2)
+        if key_padding_mask is not None:
+            raise NotImplementedError("TransformerEncoder: a padding mask is not on the HIP path (FACodec passes None)")
+        if not self.use_cln:
+            if condition is not None:
+                raise NotImplementedError("TransformerEncoder: a condition with use_cln=False is ignored by the reference; not on the HIP path")
+            return self.forward_cf(x.transpose(1, 2).contiguous()).transpose(1, 2)
+        if condition is None:
+            raise ValueError("TransformerEncoder: use_cln=True needs a condition [B, T, hidden]")
+        x = _lib.require_device_tensor(x, "TransformerEncoder input")
+        condition = _lib.require_device_tensor(condition, "TransformerEncoder condition")
+        if condition.dim() != 3 or x.dim() != 3 or condition.shape[0] != x.shape[0] or condition.shape[2] != self.encoder_hidden or condition.shape[1] < 1:
+            raise ValueError(f"TransformerEncoder: expected a condition [B, T, {self.encoder_hidden}], got {tuple(condition.shape)}")
+        if condition.device != x.device:
+            raise RuntimeError(f"TransformerEncoder: the condition is on {condition.device}, the input on {x.device}")
+        with _lib.on_device(x.device):
+            m = torch.mean(condition, dim=1)                  # every norm takes this mean (transformer.py:25)
+        return self.forward_cf(x.transpose(1, 2).contiguous(), m).transpose(1, 2)

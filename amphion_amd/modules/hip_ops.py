@@ -229,6 +229,81 @@ def layer_norm_c(x, gamma, beta, res=None, post=None, eps=1e-5, gelu=False, lens
     return y
 
 
+def layer_norm_c_style(x, style, res=None, eps=1e-5):
+    """style[b, :C] * LN(x + res) + style[b, C:] over the channel axis, LN without an affine: x [B, C, T], style [B, 2C] (or [B, 2C, 1]), one
+    scale | shift row per item (``amp_layer_norm_c_style``)"""
+    x = _lib.require_device_tensor(x, "layer_norm_c_style input")
+    style = _lib.require_device_tensor(style, "style")
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"layer_norm_c_style: expected a non-empty [B, C, T] input, got {tuple(x.shape)}")
+    B, C, T = x.shape
+    if style.numel() != B * 2 * C or style.shape[0] != B or style.device != x.device:
+        raise ValueError(f"layer_norm_c_style: expected a style of shape {(B, 2 * C)} on {x.device}, got {tuple(style.shape)} on {style.device}")
+    if res is not None:
+        res = _lib.require_device_tensor(res, "layer_norm_c_style residual")
+        if res.shape != x.shape or res.device != x.device:
+            raise ValueError(f"layer_norm_c_style: the residual must be {tuple(x.shape)} on {x.device}, got {tuple(res.shape)} on {res.device}")
+    y = torch.empty_like(x)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_layer_norm_c_style(_ptr(x), _ptr(res), _ptr(style), B, C, T, float(eps), _ptr(y), _stream(x)))
+    return y
+
+
+_embed_sum_flags = {}     # device -> the int32 word that amp_embed_sum_c raises for an index outside its table
+
+
+def _embed_sum_flag(dev):
+    flag = _embed_sum_flags.get(dev)
+    if flag is None:
+        flag = _embed_sum_flags[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return flag
+
+
+def embed_sum_check(device):
+    """Synchronise the current stream of ``device`` and raise ``AmpError`` (AMP_ERR_INVALID) if an ``embed_sum_c(..., check=False)`` since the
+    last check met an index outside its table (``amp_embed_sum_check``; the flag is cleared)"""
+    device = torch.device(device)
+    with _lib.on_device(device):
+        _lib.check(_lib.lib().amp_embed_sum_check(_ptr(_embed_sum_flag(device)), _lib.current_stream_ptr(device)))
+
+
+def embed_sum_c(codes, tables, init=None, check=True):
+    """codes integers [N, B, T], tables: N weights [rows_n, D] -> ((init + W_0[codes[0]]) + W_1[codes[1]]) + ... as [B, D, T], the fp32 adds
+    left to right (``amp_embed_sum_c``: torch's ``emb_0(c_0) + emb_1(c_1) + ...`` transposed, bit for bit).  ``init`` [B, D, T] or None.  An
+    index outside its table raises ``AmpError`` (AMP_ERR_INVALID) -- here, or with ``check=False`` at the caller's ``embed_sum_check``, which a
+    caller of several sums runs once behind them (the check synchronises)."""
+    N = len(tables)
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 3 or codes.shape[0] != N or codes.shape[1] < 1 or codes.shape[2] < 1:
+        raise ValueError(f"embed_sum_c: expected codes [{N}, B, T], got {tuple(codes.shape) if isinstance(codes, torch.Tensor) else type(codes)}")
+    if not 1 <= N <= 8:
+        raise ValueError(f"embed_sum_c: {N} tables (1..8)")
+    if codes.dtype.is_floating_point or codes.dtype == torch.bool:
+        raise TypeError(f"embed_sum_c: the codes must be integers, got {codes.dtype}")
+    if not codes.is_cuda:
+        raise RuntimeError("embed_sum_c: the codes must be a tensor on a ROCm device (there is no CPU fallback)")
+    dev = codes.device
+    tables = [_lib.require_device_tensor(w.detach(), "embedding table") for w in tables]
+    D = tables[0].shape[-1]
+    if any(w.dim() != 2 or w.shape[1] != D or w.shape[0] < 1 or w.device != dev for w in tables):
+        raise ValueError(f"embed_sum_c: every table must be [rows, {D}] on {dev}, got {[(tuple(w.shape), str(w.device)) for w in tables]}")
+    codes = codes.to(torch.int64).contiguous()
+    _, B, T = codes.shape
+    if init is not None:
+        init = _lib.require_device_tensor(init, "embed_sum_c init")
+        if tuple(init.shape) != (B, D, T) or init.device != dev:
+            raise ValueError(f"embed_sum_c: init must be {(B, D, T)} on {dev}, got {tuple(init.shape)} on {init.device}")
+    flag = _embed_sum_flag(dev)
+    y = torch.empty((B, D, T), dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * N)(*[w.data_ptr() for w in tables])
+    rows = (ctypes.c_int * N)(*[w.shape[0] for w in tables])
+    with _lib.on_device(dev):
+        st = _lib.current_stream_ptr(dev)
+        _lib.check(_lib.lib().amp_embed_sum_c(_ptr(codes), N, ptrs, rows, D, _ptr(init), B, T, _ptr(y), _ptr(flag), st))
+        if check:
+            _lib.check(_lib.lib().amp_embed_sum_check(_ptr(flag), st))
+    return y
+
+
 def dwconv_layer_norm_c(x, weight, bias, dilation, gamma, beta, lens=None, eps=1e-5, gelu=False):
     """act(LN(dwconv(x * mask))) in one launch (DDSConv's convs_sep + norms_1, modules/flow/modules.py:63-65); K = 3"""
     B, C, T = x.shape

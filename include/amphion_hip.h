@@ -98,7 +98,8 @@ typedef struct amp_gen amp_gen;
  * 146 (additive): the decoder blocks' up-sampling step amp_tconv_* and amp_set_tconv_fusion; 147 (additive): DualCodec's
  * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
  * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*;
- * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan. */
+ * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan;
+ * 152 (additive): amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (FACodec voice conversion). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -262,6 +263,15 @@ int amp_layer_norm_c(const float* x_dev, const float* res_dev, const float* gamm
 int amp_layer_norm_c_ragged(const float* x_dev, const float* res_dev, const float* gamma_dev, const float* beta_dev,
                             const float* post_dev, const int* lens_dev, int B, int C, int T, float eps, int gelu, float* y_dev,
                             void* stream);
+/* The style-adaptive LayerNorm of FACodec's conditioned transformer (models/codec/ns3_codec/transformer.py:13-32) and the
+ * `timbre_norm(x) * gamma + beta` of its decoders' inference, in one launch:
+ *     y[b, c, t] = style[b, c] * LN_c(x + res)[b, c, t] + style[b, C + c]
+ * LN_c = the LayerNorm over the channel axis without an affine of its own; style_dev [B, 2C] holds one (scale | shift) row PER ITEM.  Mean,
+ * biased variance and accumulation order are amp_layer_norm_c's: with every row of style equal to (gamma | beta) the two give the same bits.
+ * res_dev may be NULL.  Plain fp32; the same C, T and B <= 65535 as amp_layer_norm_c, and y may alias x.  Each x element is read once
+ * (C <= 256; more channels are re-read) and y is written once. */
+int amp_layer_norm_c_style(const float* x_dev, const float* res_dev, const float* style_dev, int B, int C, int T, float eps, float* y_dev,
+                           void* stream);
 /* act(LN(dwconv(x * mask))) in one launch: DDSConv's convs_sep[i] -> norms_1[i] -> gelu (modules/flow/modules.py:63-65), the
  * depthwise taps evaluated on load in amp_dwconv's order (same bits as the two launches).  K = 3, or K = 7 with C <= 1024 (ConvNeXt's
  * dwconv -> LayerNorm, vocos.py:489-496,511-518) (AMP_ERR_INVALID otherwise: run amp_dwconv + amp_layer_norm_c); dw_weight [C, 1, K], dw_bias [C] or NULL; columns t >= lens[b] of y are zero; y != x. */
@@ -325,6 +335,17 @@ int amp_affine_reverse(const float* x_dev, const float* m_dev, const float* logs
  * the mask is a 0 / 1 FACTOR on a (finite) weight. */
 int amp_embed_tokens(const long long* tokens_dev, const float* weight_dev, const int* lens_dev, int B, int T, int hidden,
                      int n_vocab, float scale, float* y_dev, void* stream);
+/* The sum of N embedding look-ups, channel-first (FACodecRedecoder.forward / vq2emb, models/codec/ns3_codec/facodec.py:698-722,736-759):
+ *     y[b, :, t] = ((init[b, :, t] + W_0[codes[0, b, t]]) + W_1[codes[1, b, t]]) + ...
+ * codes_dev int64 [N, B, T]; tables / rows: HOST arrays of N device pointers W_n [rows[n], D] and their row counts, 1 <= N <= 8; init_dev
+ * [B, D, T] or NULL; y_dev [B, D, T], not init_dev.  The fp32 adds run left to right -- the bits of torch's emb_0(c_0) + emb_1(c_1) + ...
+ * transposed -- and with init = NULL the sum starts from the row of W_0 itself.  One launch; rows are gathered as contiguous segments along D
+ * and transposed through LDS, y is stored along T.  An index outside [0, rows[n]) reads row 0 of its table instead (never out of bounds) and
+ * sets *flag_dev, one zero-initialised 32-bit word on the device that the caller owns.  amp_embed_sum_check synchronises the stream, returns
+ * AMP_ERR_INVALID if the flag was set since the last check, and clears it.  B and ceil(D / 64) <= 65535, else AMP_ERR_UNSUPPORTED. */
+int amp_embed_sum_c(const long long* codes_dev, int N, const float* const* tables, const int* rows, int D, const float* init_dev, int B, int T,
+                    float* y_dev, unsigned* flag_dev, void* stream);
+int amp_embed_sum_check(unsigned* flag_dev, void* stream);
 /* w_ceil = ceil(exp(logw) * mask * length_scale) [B, T], its running sum (int32 [B, T]) and y_len = max(sum, 1)
  * (vits.py:341-343, utils/util.py:633). */
 int amp_durations(const float* logw_dev, const int* lens_dev, int B, int T, float length_scale, float* w_ceil_dev, int* cum_dev,
