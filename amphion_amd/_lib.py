@@ -196,6 +196,11 @@ _SIGNATURES = {
     "amp_dsconv_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "amp_dsconv_destroy": (None, [c_void_p]),
     "amp_gelu": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "amp_silu": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "amp_swiglu": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "amp_rms_norm_c_adaptive": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "amp_rope_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                   c_void_p, c_void_p]),
     "amp_layer_norm_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_layer_norm_c_style": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -1,0 +1,421 @@
+// The kernels of the non-autoregressive Llama of Vevo / MaskGCT (models/vc/flow_matching_transformer/llama_nar.py: DiffLlama), the parts
+// the pointwise GEMM (pw_f16x3.hip) does not cover:
+//     amp_rope_attention        non-causal multi-head self-attention with rotary position embedding and a key mask, one launch
+//     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
+//     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
+// Everything is channel-first [B, C, T] fp32.  Deterministic: no atomics on data (the attention kernel ORs the op-level range flag).
+//
+// ---- amp_rope_attention ---------------------------------------------------------------------------------------------------------
+// A workgroup of four waves owns 128 queries of one (item, head); a wave owns 32 of them and walks the keys in tiles of 64 with the
+// online softmax.  Channel-first suits the TRANSPOSED products (f16x3_device.h for the MFMA layouts):
+//     S^T [tk, tq] = K'^T Q'      A = K'^T (row = key, k = channel), B = Q' (k = channel, column = query)
+//     O   [d,  tq] = V  P^T       A = V    (row = channel, k = key), B = P^T (k = key, column = query)
+// so a lane owns ONE query column in both accumulators: the running maximum, the running sum and the rescale are per-lane scalars
+// (the two lanes l and l ^ 32 share a query and hold 16 of every 32 keys each: one cross-lane maximum per tile, one sum at the end).
+// The S^T accumulator is the next product's B operand as it stands: registers 8c' .. 8c' + 7 of row block rb are the eight k-slots of
+// key chunk c = 2 rb + c', which fixes the order in which V's A fragment takes its keys -- key(hi, j) = 16 c + 8 (j >> 2) + 4 hi + (j & 3),
+// two 8-byte reads of V's [channel][key] image.  No P ever goes through LDS.
+// Q' = RoPE(q) is split once per wave into registers (a lane loads the channels of its own fragment and their rotate-half partners);
+// K' = RoPE(k) and V go global -> registers -> LDS as hi / lo f16 planes, the loads of tile i + 1 issued before the products of tile i.
+// Operands are staged after an exact x16 like every f16x3 kernel (|q'|, |k'|, |v| <= 4094, range flag beyond); P in [0, 1] after an
+// exact x1024.  A masked key (or one beyond T) is staged as ZERO in K' and V and its score is -inf, so it contributes exactly 0 whatever
+// finite value its columns hold.
+#include <hip/hip_runtime.h>
+
+#include "amp_host.h"
+#include "amphion_hip.h"
+#include "f16x3_device.h"
+
+namespace amp {
+
+constexpr int AT_NW = 4;              // waves per workgroup
+constexpr int AT_TQ = 32 * AT_NW;     // queries per workgroup
+constexpr int AT_TK = 64;             // keys per tile
+constexpr int AT_DK = 64;             // head dimension
+constexpr int AT_VS = AT_TK + 4;      // V image row stride in f16: 34 dwords, the 32 rows of a fragment read fall on distinct bank pairs
+constexpr int AT_MAX_T = 32768;
+
+struct AttnArgs {
+    const float* q;
+    const float* k;
+    const float* v;
+    long long bstride;             // elements between items of q / k / v
+    const float* cs;               // [T, 32]
+    const float* sn;
+    const unsigned char* mask;     // [B, T] or nullptr
+    float* out;                    // [B, H * 64, T]
+    int H, T;
+    float c;                       // scale / 256: un-does the two x16 of the staged operands
+    unsigned* range_flag;
+};
+
+__global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) {
+    __shared__ uint4 kpl[2][8 * AT_TK];                                       // [plane][channel octet][key] x 8 f16
+    __shared__ __attribute__((aligned(16))) _Float16 vpl[2][AT_DK * AT_VS];   // [plane][channel][key]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int b = blockIdx.y / a.H, h = blockIdx.y - b * a.H;
+    const int T = a.T;
+    const size_t head = (size_t)b * (size_t)a.bstride + (size_t)h * AT_DK * T;
+    const float* __restrict__ qb = a.q + head;
+    const float* __restrict__ kb = a.k + head;
+    const float* __restrict__ vb = a.v + head;
+    const unsigned char* __restrict__ mk = a.mask ? a.mask + (size_t)b * T : nullptr;
+    float range_max = 0.f;
+
+    // ---- Q' fragments: lane (l31, hi) holds channels 16 s + 8 hi + j of query l31; channel i < 32 and its partner i + 32 are s and s + 2
+    const int tq = blockIdx.x * AT_TQ + 32 * w + l31;
+    const int tqc = tq < T ? tq : T - 1;
+    Frag qh[4], ql[4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int i = 16 * p + 8 * hi + j;
+            const float x1 = qb[(size_t)i * T + tqc], x2 = qb[(size_t)(i + 32) * T + tqc];
+            const float c = a.cs[(size_t)tqc * 32 + i], s = a.sn[(size_t)tqc * 32 + i];
+            const float r1 = (x1 * c - x2 * s) * 16.f, r2 = (x2 * c + x1 * s) * 16.f;
+            range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1), __builtin_fabsf(r2)));
+            _Float16 hh, ll;
+            split_f16(r1, hh, ll);
+            qh[p].h[j] = hh; ql[p].h[j] = ll;
+            split_f16(r2, hh, ll);
+            qh[p + 2].h[j] = hh; ql[p + 2].h[j] = ll;
+        }
+    }
+
+    // ---- the staged tile: thread (key = lane, wave w) takes K channels 8 w .. 8 w + 7 with their partners (two whole octets after the
+    // rotation) and V channels w, w + 4, ...
+    float kr[16], vr[16];
+    float4 cr[2], sr[2];
+    bool valid;
+    auto load_tile = [&](int tk0) {
+        const int tk = tk0 + lane;
+        const int tkc = tk < T ? tk : T - 1;
+        valid = tk < T && (!mk || mk[tkc] != 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            kr[j] = kb[(size_t)(8 * w + j) * T + tkc];
+            kr[8 + j] = kb[(size_t)(8 * w + j + 32) * T + tkc];
+        }
+        const float4* cp = reinterpret_cast<const float4*>(a.cs + (size_t)tkc * 32 + 8 * w);
+        const float4* sp = reinterpret_cast<const float4*>(a.sn + (size_t)tkc * 32 + 8 * w);
+        cr[0] = cp[0]; cr[1] = cp[1];
+        sr[0] = sp[0]; sr[1] = sp[1];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) vr[i] = vb[(size_t)(w + 4 * i) * T + tkc];
+    };
+
+    f32x16 O[2][1];
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[db][0][r] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    constexpr float LOG2E = 1.4426950408889634f;
+
+    const int nkt = (T + AT_TK - 1) / AT_TK;
+    load_tile(0);
+    for (int kt = 0; kt < nkt; ++kt) {
+        __syncthreads();                                   // every wave is done reading the previous tile
+        {
+            const float cc[8] = {cr[0].x, cr[0].y, cr[0].z, cr[0].w, cr[1].x, cr[1].y, cr[1].z, cr[1].w};
+            const float ss[8] = {sr[0].x, sr[0].y, sr[0].z, sr[0].w, sr[1].x, sr[1].y, sr[1].z, sr[1].w};
+            float r1[8], r2[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float u1 = (kr[j] * cc[j] - kr[8 + j] * ss[j]) * 16.f, u2 = (kr[8 + j] * cc[j] + kr[j] * ss[j]) * 16.f;
+                r1[j] = valid ? u1 : 0.f;
+                r2[j] = valid ? u2 : 0.f;
+                range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1[j]), __builtin_fabsf(r2[j])));
+            }
+            uint2 h0, l0, h1, l1;
+            split4_f16(amp_f32x2{r1[0], r1[1]}, amp_f32x2{r1[2], r1[3]}, h0, l0);
+            split4_f16(amp_f32x2{r1[4], r1[5]}, amp_f32x2{r1[6], r1[7]}, h1, l1);
+            kpl[0][w * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
+            kpl[1][w * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+            split4_f16(amp_f32x2{r2[0], r2[1]}, amp_f32x2{r2[2], r2[3]}, h0, l0);
+            split4_f16(amp_f32x2{r2[4], r2[5]}, amp_f32x2{r2[6], r2[7]}, h1, l1);
+            kpl[0][(w + 4) * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
+            kpl[1][(w + 4) * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float u = valid ? vr[i] * 16.f : 0.f;
+                range_max = __builtin_fmaxf(range_max, __builtin_fabsf(u));
+                _Float16 hh, ll;
+                split_f16(u, hh, ll);
+                vpl[0][(w + 4 * i) * AT_VS + lane] = hh;
+                vpl[1][(w + 4 * i) * AT_VS + lane] = ll;
+            }
+        }
+        const unsigned long long km = __ballot(valid);     // the tile's valid keys: lane = key in every wave
+        __syncthreads();
+        if (kt + 1 < nkt) load_tile((kt + 1) * AT_TK);     // in flight behind the products below
+
+        // ---- S^T = K'^T Q' over the 64 channels
+        f32x16 S[2][1];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) S[rb][0][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            Frag ah[2], al[2];
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                ah[rb].u = kpl[0][(2 * s + hi) * AT_TK + 32 * rb + l31];
+                al[rb].u = kpl[1][(2 * s + hi) * AT_TK + 32 * rb + l31];
+            }
+            mfma3_tiles<2, 1>(S, ah, al, &qh[s], &ql[s]);
+        }
+
+        // ---- online softmax of the lane's query column (its 32 of the tile's 64 keys)
+        float sv[2][16];
+        float mx = -INFINITY;
+        const bool all_valid = km == ~0ull;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            const unsigned mw = (unsigned)(km >> (32 * rb)) >> (4 * hi);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float s = S[rb][0][r] * a.c;
+                if (!all_valid) s = ((mw >> acc_row(r)) & 1u) ? s : -INFINITY;
+                sv[rb][r] = s;
+                mx = __builtin_fmaxf(mx, s);
+            }
+        }
+        mx = __builtin_fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = __builtin_fmaxf(m, mx);
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;          // no valid key so far: every p below is exp2(-inf) = 0
+        if (!__all(m_new == m)) {                                      // the running maximum moved: rescale what is accumulated
+            const float alpha = __builtin_amdgcn_exp2f((m - m_use) * LOG2E);
+            l *= alpha;
+#pragma unroll
+            for (int db = 0; db < 2; ++db)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) O[db][0][r] *= alpha;
+            m = m_new;
+        }
+        Frag ph[4], pl[4];
+        float psum = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float p = __builtin_amdgcn_exp2f((sv[c >> 1][8 * (c & 1) + j] - m_use) * LOG2E);
+                psum += p;
+                _Float16 hh, ll;
+                split_f16(p * 1024.f, hh, ll);
+                ph[c].h[j] = hh; pl[c].h[j] = ll;
+            }
+        }
+        l += psum;
+
+        // ---- O += V P^T: chunk c's k-slot (hi, j) is key 16 c + 8 (j >> 2) + 4 hi + (j & 3)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            Frag vh[2], vl[2];
+#pragma unroll
+            for (int db = 0; db < 2; ++db) {
+                const int off = (32 * db + l31) * AT_VS + 16 * c + 4 * hi;
+                const uint2 x0 = *reinterpret_cast<const uint2*>(&vpl[0][off]), x1 = *reinterpret_cast<const uint2*>(&vpl[0][off + 8]);
+                const uint2 y0 = *reinterpret_cast<const uint2*>(&vpl[1][off]), y1 = *reinterpret_cast<const uint2*>(&vpl[1][off + 8]);
+                vh[db].u = make_uint4(x0.x, x0.y, x1.x, x1.y);
+                vl[db].u = make_uint4(y0.x, y0.y, y1.x, y1.y);
+            }
+            mfma3_tiles<2, 1>(O, vh, vl, &ph[c], &pl[c]);
+        }
+    }
+
+    const float lt = l + __shfl_xor(l, 32);
+    const float inv = (1.0f / lt) * (1.0f / 16384.f);      // x16 of V, x1024 of P
+    if (tq < T) {
+        float* ob = a.out + ((size_t)blockIdx.y * AT_DK) * T + tq;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ob[(size_t)acc_row(r, hi, 32 * db) * T] = O[db][0][r] * inv;
+    }
+    raise_range(a.range_flag, range_max, lane);
+}
+
+// ---- amp_rms_norm_c_adaptive: y[b, c, t] = w[b, c] * (x[b, c, t] * rsqrt(mean_c x[b, :, t]^2 + eps)) ------------------------------
+// amp_layer_norm_c_style's workgroup: 32 time columns x 8 channel groups, thread (tx, g) holds channels g, g + 8, ... of column tx in
+// registers (NC of them; more are re-read), rows are read as 128-B segments, the reduction over C goes through LDS in a fixed order.
+constexpr int RN_TT = 32, RN_G = 8;
+template <int NC>
+__global__ __launch_bounds__(256) void rms_norm_c_adaptive_kernel(const float* __restrict__ x, const float* __restrict__ w, long long wbs,
+                                                                  float* __restrict__ y, int C, int T, float eps) {
+    __shared__ float red[RN_G][RN_TT + 1];
+    const int tx = threadIdx.x & (RN_TT - 1), g = threadIdx.x / RN_TT;
+    const int t = blockIdx.x * RN_TT + tx;
+    const int b = blockIdx.y;
+    const bool ok = t < T;
+    const size_t base = (size_t)b * C * T + (ok ? t : 0);
+    const float* xb = x + base;
+    const float* wb = w + (size_t)b * (size_t)wbs;
+    float v[NC];
+    float part = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int c = g + RN_G * i;
+        v[i] = xb[(size_t)(c < C ? c : C - 1) * T];
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        v[i] = (ok && g + RN_G * i < C) ? v[i] : 0.f;
+        part = fmaf(v[i], v[i], part);
+    }
+    for (int c = g + RN_G * NC; c < C; c += RN_G) {
+        const float u = ok ? xb[(size_t)c * T] : 0.f;
+        part = fmaf(u, u, part);
+    }
+    red[g][tx] = part;
+    __syncthreads();
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < RN_G; ++k) s += red[k][tx];
+    const float rs = 1.0f / sqrtf(s / (float)C + eps);
+    if (!ok) return;
+    float* yb = y + base;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int c = g + RN_G * i;
+        if (c < C) yb[(size_t)c * T] = wb[c] * (v[i] * rs);
+    }
+    for (int c = g + RN_G * NC; c < C; c += RN_G) yb[(size_t)c * T] = wb[c] * (xb[(size_t)c * T] * rs);
+}
+
+// ---- amp_silu / amp_swiglu ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float silu_f(float v) { return v / (1.0f + expf(-v)); }
+
+// element-wise, amp_gelu's shape: vec = both bases 16-byte aligned -- threads [0, n / 4) take quads, the next n % 4 threads the tail
+__global__ __launch_bounds__(256) void silu_kernel(const float* x, float* y, size_t n, int vec) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (vec) {
+        const size_t nq = n >> 2;
+        if (i < nq) {
+            const float4 t = reinterpret_cast<const float4*>(x)[i];
+            reinterpret_cast<float4*>(y)[i] = make_float4(silu_f(t.x), silu_f(t.y), silu_f(t.z), silu_f(t.w));
+        } else {
+            const size_t k = 4 * nq + (i - nq);
+            if (k < n) y[k] = silu_f(x[k]);
+        }
+    } else if (i < n) {
+        y[i] = silu_f(x[i]);
+    }
+}
+
+// gu [B, 2F, T]: item blockIdx.y, n = F * T elements of gate followed by n of up.  vec: n % 4 == 0 and both bases 16-byte aligned.
+__global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ gu, float* __restrict__ y, size_t n, int vec) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const float* g = gu + (size_t)blockIdx.y * 2 * n;
+    const float* u = g + n;
+    float* yb = y + (size_t)blockIdx.y * n;
+    if (vec) {
+        if (i < (n >> 2)) {
+            const float4 a = reinterpret_cast<const float4*>(g)[i], c = reinterpret_cast<const float4*>(u)[i];
+            reinterpret_cast<float4*>(yb)[i] = make_float4(silu_f(a.x) * c.x, silu_f(a.y) * c.y, silu_f(a.z) * c.z, silu_f(a.w) * c.w);
+        }
+    } else if (i < n) {
+        yb[i] = silu_f(g[i]) * u[i];
+    }
+}
+
+}  // namespace amp
+
+using namespace amp;
+
+extern "C" {
+
+int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
+                       const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
+                       void* stream) {
+    if (!q_dev || !k_dev || !v_dev || !cos_dev || !sin_dev || !out_dev) { set_error("amp_rope_attention: null argument"); return AMP_ERR_INVALID; }
+    if (dk != AT_DK) { set_error("amp_rope_attention: head dimension %d is not covered (dk = %d only)", dk, AT_DK); return AMP_ERR_INVALID; }
+    if (B < 1 || H < 1 || T < 1) { set_error("amp_rope_attention: B=%d H=%d T=%d", B, H, T); return AMP_ERR_INVALID; }
+    if (T > AT_MAX_T) { set_error("amp_rope_attention: T=%d is beyond %d", T, AT_MAX_T); return AMP_ERR_INVALID; }
+    if ((long long)B * H > 65535) { set_error("amp_rope_attention: B*H=%lld is beyond the grid (65535)", (long long)B * H); return AMP_ERR_INVALID; }
+    if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("amp_rope_attention: scale=%g", (double)scale); return AMP_ERR_INVALID; }
+    if (batch_stride == 0) batch_stride = (long long)H * dk * T;
+    if (batch_stride < (long long)H * dk * T) { set_error("amp_rope_attention: batch stride %lld < H*dk*T", batch_stride); return AMP_ERR_INVALID; }
+    if ((reinterpret_cast<uintptr_t>(cos_dev) | reinterpret_cast<uintptr_t>(sin_dev)) & 15) {
+        set_error("amp_rope_attention: cos / sin must be 16-byte aligned");
+        return AMP_ERR_INVALID;
+    }
+    const size_t span = (size_t)(B - 1) * (size_t)batch_stride + (size_t)H * dk * T;
+    const float* olo = out_dev;
+    const float* ohi = out_dev + (size_t)B * H * dk * T;
+    for (const float* p : {q_dev, k_dev, v_dev})
+        if (p < ohi && olo < p + span) { set_error("amp_rope_attention: out must not overlap q / k / v"); return AMP_ERR_INVALID; }
+    if (T == 1) {
+        // One key: the softmax over it is exactly 1 whatever q and k hold (the item's one key is valid, see the header), so the attention
+        // is the identity on v and there is no product to form.  A strided copy returns v's bits, as the fp32 reference does (1.0f * v),
+        // where the split-f16 operand of the kernel would return 22 of its 24 mantissa bits.
+        AMP_HIP(hipMemcpy2DAsync(out_dev, (size_t)H * dk * sizeof(float), v_dev, (size_t)batch_stride * sizeof(float),
+                                 (size_t)H * dk * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return AMP_OK;
+    }
+    AttnArgs a{};
+    a.q = q_dev; a.k = k_dev; a.v = v_dev;
+    a.bstride = batch_stride;
+    a.cs = cos_dev; a.sn = sin_dev;
+    a.mask = key_mask_dev;
+    a.out = out_dev;
+    a.H = H; a.T = T;
+    a.c = scale * (1.0f / 256.f);
+    a.range_flag = range_flag_for_current_device();
+    const dim3 grid((unsigned)((T + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
+    note_kernel("rope_attention_kernel");
+    note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
+              "rope attention B=%d H=%d dk=%d T=%d mask=%d", B, H, dk, T, key_mask_dev ? 1 : 0);
+    hipLaunchKernelGGL(rope_attention_kernel, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+    AMP_HIP(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,
+                            void* stream) {
+    if (!x_dev || !w_dev || !y_dev || B < 1 || C < 1 || T < 1 || B > 65535 || w_batch_stride < 0 || !(eps >= 0.f)) {
+        set_error("amp_rms_norm_c_adaptive: bad argument (B=%d C=%d T=%d w_batch_stride=%lld)", B, C, T, w_batch_stride);
+        return AMP_ERR_INVALID;
+    }
+    const dim3 grid((unsigned)((T + RN_TT - 1) / RN_TT), (unsigned)B);
+    auto kern = C <= 32 * RN_G ? rms_norm_c_adaptive_kernel<32> : rms_norm_c_adaptive_kernel<128>;
+    note_kernel("rms_norm_c_adaptive_kernel", C <= 32 * RN_G ? 32 : 128);
+    note_work((unsigned long long)grid.x * grid.y, 0.0, 8.0 * (double)B * C * T / 1e6, "adaptive rms norm C=%d T=%d B=%d", C, T, B);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, x_dev, w_dev, w_batch_stride, y_dev, C, T, eps);
+    AMP_HIP(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp_silu(const float* x_dev, long long n, float* y_dev, void* stream) {
+    if (!x_dev || !y_dev || n <= 0) { set_error("amp_silu: bad argument (n=%lld)", n); return AMP_ERR_INVALID; }
+    const int vec = ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(y_dev)) & 15) == 0 ? 1 : 0;
+    const long long threads = vec ? (n >> 2) + (n & 3) : n;
+    const long long blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffll) { set_error("amp_silu: n=%lld is beyond the grid", n); return AMP_ERR_UNSUPPORTED; }
+    note_kernel("silu_kernel");
+    note_work((unsigned long long)blocks, 0.0, 8.0 * (double)n / 1e6, "silu n=%lld", n);
+    hipLaunchKernelGGL(silu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x_dev, y_dev, (size_t)n, vec);
+    AMP_HIP(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp_swiglu(const float* gu_dev, int B, int F, int T, float* y_dev, void* stream) {
+    if (!gu_dev || !y_dev || B < 1 || F < 1 || T < 1 || B > 65535) { set_error("amp_swiglu: bad argument (B=%d F=%d T=%d)", B, F, T); return AMP_ERR_INVALID; }
+    const size_t n = (size_t)F * T;
+    const float* ylo = y_dev;
+    const float* yhi = y_dev + (size_t)B * n;
+    if (gu_dev < yhi && ylo < gu_dev + 2 * (size_t)B * n) { set_error("amp_swiglu: y must not overlap gu"); return AMP_ERR_INVALID; }
+    const int vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(gu_dev) | reinterpret_cast<uintptr_t>(y_dev)) & 15) == 0 ? 1 : 0;
+    const size_t threads = vec ? n >> 2 : n;
+    const size_t blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffull) { set_error("amp_swiglu: F*T=%zu is beyond the grid", n); return AMP_ERR_UNSUPPORTED; }
+    note_kernel("swiglu_kernel");
+    note_work((unsigned long long)blocks * B, 0.0, 12.0 * (double)B * n / 1e6, "swiglu F=%d T=%d B=%d", F, T, B);
+    hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, gu_dev, y_dev, n, vec);
+    AMP_HIP(hipGetLastError());
+    return AMP_OK;
+}
+
+}  // extern "C"

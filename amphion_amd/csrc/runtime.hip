@@ -197,8 +197,9 @@ extern "C" {
 // 148 (additive): FACodec's anti-aliased residual unit amp_aa_unit_* and amp_set_aa_unit_fusion (codec.hip, aa_unit_f16x3.hip);
 // 149 (additive): SpeechTokenizer's amp_elu_pad (seanet.hip), amp_lstm_* (lstm.hip) and amp_evq_* (evq.hip); 150 (additive): amp_dsconv_* and amp_gelu;
 // 151 (additive): amp_set_strip_fit and amp_pair_strip_plan (fitted strips of the fused-pair strip kernel, conv_host.hip strip_geometry);
-// 152 (additive): FACodec voice conversion's amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (vits_text.hip)
-int amp_version(void) { return 152; }
+// 152 (additive): FACodec voice conversion's amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (vits_text.hip);
+// 153 (additive): the flow-matching transformer's amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (llama_nar.hip)
+int amp_version(void) { return 153; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

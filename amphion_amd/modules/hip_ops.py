@@ -424,3 +424,124 @@ def gauss_sample(m, logs, noise, noise_scale):
     out = torch.empty_like(m)
     _lib.check(_lib.lib().amp_gauss_sample(_ptr(m), _ptr(logs), _ptr(noise), m.numel(), float(noise_scale), _ptr(out), _stream(m)))
     return out
+
+
+# ---- the non-autoregressive Llama of Vevo / MaskGCT (csrc/llama_nar.hip) ----------------
+def silu(x, out=None):
+    """nn.SiLU element-wise (``amp_silu``); ``out`` may be ``x``"""
+    x = _lib.require_device_tensor(x, "silu input")
+    if x.numel() == 0:
+        raise ValueError(f"silu: empty input {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"silu: out must be a contiguous float32 {tuple(x.shape)} on {x.device}")
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_silu(_ptr(x), x.numel(), _ptr(out), _stream(x)))
+    return out
+
+
+def swiglu(gu):
+    """gu [B, 2F, T], the output of one stacked gate | up GEMM -> silu(gu[:, :F]) * gu[:, F:] [B, F, T] (``amp_swiglu``)"""
+    gu = _lib.require_device_tensor(gu, "swiglu input")
+    if gu.dim() != 3 or gu.numel() == 0 or gu.shape[1] % 2:
+        raise ValueError(f"swiglu: expected a non-empty [B, 2F, T] input, got {tuple(gu.shape)}")
+    B, F2, T = gu.shape
+    y = torch.empty((B, F2 // 2, T), dtype=torch.float32, device=gu.device)
+    with _lib.on_device(gu.device):
+        _lib.check(_lib.lib().amp_swiglu(_ptr(gu), B, F2 // 2, T, _ptr(y), _stream(gu)))
+    return y
+
+
+def rms_norm_c_adaptive(x, w, eps=1e-6):
+    """w[b, c] * x[b, c, t] * rsqrt(mean_c x[b, :, t]^2 + eps): x [B, C, T]; w [B, C] or [B, C, 1], one row per item, which may be a slice
+    of a wider tensor -- it is read in place through its batch stride (``amp_rms_norm_c_adaptive``)"""
+    x = _lib.require_device_tensor(x, "rms_norm_c_adaptive input")
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"rms_norm_c_adaptive: expected a non-empty [B, C, T] input, got {tuple(x.shape)}")
+    B, C, T = x.shape
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.device != x.device:
+        raise ValueError(f"rms_norm_c_adaptive: the weight must be a float32 tensor on {x.device}")
+    if w.dim() == 3 and w.shape[2] == 1:
+        w = w[:, :, 0]
+    if w.dim() != 2 or tuple(w.shape) != (B, C):
+        raise ValueError(f"rms_norm_c_adaptive: expected a weight of shape {(B, C)}, got {tuple(w.shape)}")
+    if (C > 1 and w.stride(1) != 1) or (B > 1 and w.stride(0) < C):
+        w = w.contiguous()
+    y = torch.empty_like(x)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_rms_norm_c_adaptive(_ptr(x), _ptr(w), int(w.stride(0)) if B > 1 else C, B, C, T, float(eps), _ptr(y), _stream(x)))
+    return y
+
+
+_rope_tables = {}     # (T, dk, theta, device) -> (cos, sin) [T, dk / 2]
+
+
+def rope_tables(T, dk, device, theta=10000.0):
+    """cos, sin [T, dk/2] fp32 as HF's ``LlamaRotaryEmbedding`` computes them (inv_freq = theta^(-2i/dk), positions 0 .. T-1, fp32), once
+    per (T, dk, theta, device)"""
+    key = (int(T), int(dk), float(theta), str(device))
+    t = _rope_tables.get(key)
+    if t is None:
+        inv_freq = 1.0 / (theta ** (torch.arange(0, dk, 2, dtype=torch.int64).to(device=device, dtype=torch.float32) / dk))
+        freqs = torch.arange(T, device=device, dtype=torch.float32)[:, None] * inv_freq[None, :]
+        if len(_rope_tables) >= 64:
+            _rope_tables.clear()
+        t = _rope_tables[key] = (freqs.cos().contiguous(), freqs.sin().contiguous())
+    return t
+
+
+def _rows_view(t, C, T, bstride):
+    """is ``t`` [B, C, T] laid out as the kernel reads it: unit column stride, rows T apart, batch stride ``bstride``"""
+    return t.stride(2) == 1 and (C == 1 or t.stride(1) == T) and (t.shape[0] == 1 or t.stride(0) == bstride)
+
+
+def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
+    """Non-causal multi-head self-attention with rotary position embedding (HF's rotate-half form) and a KEY mask (``amp_rope_attention``).
+
+    q, k, v [B, H*dk, T] channel-first: contiguous tensors, or the three row blocks of one stacked [B, 3*H*dk, T] GEMM output (read in
+    place: no copy).  cos, sin [T, dk/2] (``rope_tables``).  key_mask [B, T] bool / uint8, 1 = valid, any pattern, at least one valid key
+    per item; None = all valid.  -> [B, H*dk, T].  dk = 64.  Under the "f32" precision the same formula runs as RoPE in torch plus
+    ``scaled_dot_product_attention`` (not the hot path)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v"), (cos, "cos"), (sin, "sin")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError(f"rope_attention: {name} must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or k.device != q.device or v.device != q.device:
+        raise ValueError(f"rope_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    B, C, T = q.shape
+    H = int(n_heads)
+    if H < 1 or C % H:
+        raise ValueError(f"rope_attention: {C} channels do not divide into {H} heads")
+    dk = C // H
+    if dk != 64:
+        raise ValueError(f"rope_attention: head dimension {dk} is not covered (dk = 64 only)")
+    if B < 1 or T < 1:
+        raise ValueError(f"rope_attention: empty input {tuple(q.shape)}")
+    if tuple(cos.shape) != (T, dk // 2) or tuple(sin.shape) != (T, dk // 2) or cos.device != q.device or sin.device != q.device:
+        raise ValueError(f"rope_attention: cos and sin must be {(T, dk // 2)} on {q.device}, got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    cos, sin = cos.contiguous(), sin.contiguous()
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
+            raise ValueError(f"rope_attention: key_mask must be a {(B, T)} tensor on {q.device}")
+        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
+            key_mask = (key_mask != 0).to(torch.uint8)
+        key_mask = key_mask.contiguous()
+    scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
+    with _lib.on_device(q.device):
+        if _lib.get_precision() == "f32":
+            def rope(x):
+                x = x.reshape(B, H, dk, T).transpose(2, 3)
+                c, s = torch.cat((cos, cos), -1), torch.cat((sin, sin), -1)
+                return x * c + torch.cat((-x[..., dk // 2:], x[..., : dk // 2]), -1) * s
+            m = None if key_mask is None else key_mask.bool()[:, None, None, :]
+            o = torch.nn.functional.scaled_dot_product_attention(rope(q), rope(k), v.reshape(B, H, dk, T).transpose(2, 3), attn_mask=m, scale=scale)
+            return o.transpose(2, 3).reshape(B, C, T).contiguous()
+        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
+        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            bstride = C * T
+        out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().amp_rope_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), _ptr(key_mask), B, H, dk, T, scale,
+                                                 _ptr(out), _stream(q)))
+    return out

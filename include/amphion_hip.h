@@ -99,7 +99,8 @@ typedef struct amp_gen amp_gen;
  * amp_dwconv_layer_norm_c_causal, amp_fvq_encode_ex, amp_fvq_decode_add and amp_semantic_prepare; 148 (additive): FACodec's anti-aliased
  * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*;
  * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan;
- * 152 (additive): amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (FACodec voice conversion). */
+ * 152 (additive): amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (FACodec voice conversion);
+ * 153 (additive): amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (the flow-matching transformer of Vevo). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -881,6 +882,46 @@ void amp_dsconv_destroy(amp_dsconv* h);
  * i < n.  y may alias x; any 4-byte alignment (16-byte accesses where both bases allow).  NULL pointers or n <= 0: AMP_ERR_INVALID; more than
  * 2^31 - 1 workgroups: AMP_ERR_UNSUPPORTED; judged on the host alone. */
 int amp_gelu(const float* x_dev, long long n, float* y_dev, void* stream);
+
+/* ---- The non-autoregressive Llama of Vevo / MaskGCT (csrc/llama_nar.hip; models/vc/flow_matching_transformer/llama_nar.py: DiffLlama).
+ * Channel-first [B, C, T] fp32 like everything here; the Linears are amp_pw_forward.  Deterministic, no workspace, no allocation and no
+ * synchronisation; every argument is judged on the host before anything is launched. ---- */
+
+/* Non-causal multi-head self-attention with rotary position embedding and a key mask, in one launch (flash-style: no [T, T] tensor):
+ *     out[b, h*dk + d, t] = sum_s softmax_s( scale * <rope(q)[b, h, :, t], rope(k)[b, h, :, s]> + mask(b, s) ) v[b, h*dk + d, s]
+ * q, k, v [B, H*dk, T] with rows T apart and ONE batch stride of batch_stride elements (0 = dense, H*dk*T): the three row blocks of a
+ * stacked q | k | v GEMM output [B, 3*H*dk, T] are read in place (batch_stride = 3*H*dk*T).  out [B, H*dk, T] dense, not overlapping them.
+ * cos, sin [T, dk/2] fp32, 16-byte aligned: HF's LlamaRotaryEmbedding (inv_freq = theta^(-2i/dk), positions 0 .. T-1).  The rotation is
+ * HF's rotate-half form, x'[i] = x[i] cos[t, i] - x[i + dk/2] sin[t, i], x'[i + dk/2] = x[i + dk/2] cos[t, i] + x[i] sin[t, i] for i < dk/2 --
+ * NOT the interleaved-pair form -- applied to q and k while they are staged.
+ * key_mask [B, T] bytes, 1 = valid, any pattern; NULL = all valid.  The mask applies to KEYS only: every query column is computed, padded
+ * positions included, as the reference does.  A masked key contributes exactly 0 whatever finite value its k / v columns hold.  Every item
+ * needs at least one valid key (an item without one gets NaN columns; the reference gives it the mean of v).
+ * scale: 1/sqrt(dk) (any positive finite value).
+ * Arithmetic: both products are split-f16 MFMA (hi*hi + hi*lo + lo*hi, fp32 accumulate) whatever amp_set_precision says -- the exact-fp32
+ * route of the drop-in modules is RoPE in torch + scaled_dot_product_attention; the softmax is an online fp32 softmax.  rope(q), rope(k) and v
+ * are staged after an exact x16 and take part in the op-level range guard (amp_range_check; masked keys do not).
+ * T = 1 is not a launch of the kernel: the softmax over one key is exactly 1, so out is a strided copy of v (its bits, no range guard).
+ * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk != 64, B, H or T < 1, T > 32768, B*H > 65535, batch_stride below
+ * H*dk*T, a misaligned cos / sin, out overlapping q / k / v. */
+int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
+                       const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
+                       void* stream);
+
+/* LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis:
+ *     y[b, c, t] = w[b, c] * ( x[b, c, t] * rsqrt( mean_c x[b, :, t]^2 + eps ) )
+ * x [B, C, T]; w one row of C weights PER ITEM, w_batch_stride elements apart (>= 0; the rows may be a slice of a wider tensor, e.g. of the
+ * stacked to_weight GEMM of all norms of a model).  Plain fp32, the workgroup shape of amp_layer_norm_c_style; any C, T >= 1, B <= 65535;
+ * y may alias x.  Each x element is read once for C <= 1024 (more channels are re-read).  Bad arguments: AMP_ERR_INVALID. */
+int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,
+                            void* stream);
+
+/* Element-wise nn.SiLU, y[i] = x[i] / (1 + exp(-x[i])), i < n; the contract of amp_gelu (y may alias x, any 4-byte alignment). */
+int amp_silu(const float* x_dev, long long n, float* y_dev, void* stream);
+/* LlamaMLP's act_fn(gate_proj(x)) * up_proj(x) on the output of ONE stacked gate | up GEMM: gu [B, 2F, T] with the gate in rows [0, F) and
+ * up in rows [F, 2F) -> y[b, f, t] = silu(gu[b, f, t]) * gu[b, F + f, t], y [B, F, T] not overlapping gu.  B <= 65535; bad arguments
+ * AMP_ERR_INVALID, more than 2^31 - 1 workgroups per item AMP_ERR_UNSUPPORTED. */
+int amp_swiglu(const float* gu_dev, int B, int F, int T, float* y_dev, void* stream);
 
 #ifdef __cplusplus
 }
