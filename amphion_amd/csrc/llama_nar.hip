@@ -31,7 +31,6 @@ namespace amp {
 constexpr int AT_NW = 4;              // waves per workgroup
 constexpr int AT_TQ = 32 * AT_NW;     // queries per workgroup
 constexpr int AT_TK = 64;             // keys per tile
-constexpr int AT_DK = 64;             // head dimension
 constexpr int AT_VS = AT_TK + 4;      // V image row stride in f16: 34 dwords, the 32 rows of a fragment read fall on distinct bank pairs
 constexpr int AT_MAX_T = 32768;
 
@@ -40,17 +39,23 @@ struct AttnArgs {
     const float* k;
     const float* v;
     long long bstride;             // elements between items of q / k / v
-    const float* cs;               // [T, 32]
+    const float* cs;               // [T, DK / 2]
     const float* sn;
     const unsigned char* mask;     // [B, T] or nullptr
-    float* out;                    // [B, H * 64, T]
+    float* out;                    // [B, H * DK, T]
     int H, T;
-    float c;                       // scale / 256: un-does the two x16 of the staged operands
+    float c;                       // scale / 256: un-does the two x16 of the staged operands (a power of two at DK = 64 only: one rounding at 96)
     unsigned* range_flag;
 };
 
+// DK = 64 or 96.  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
+// S, ND = DK / 32 the row blocks of O, HO = DK / 16 the channel octets per half: wave w stages octets w, w + 4, ... < HO with their partners
+// (at DK = 96 waves 0 and 1 take two octet pairs, waves 2 and 3 one).
+template <int DK>
 __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) {
-    __shared__ uint4 kpl[2][8 * AT_TK];                                       // [plane][channel octet][key] x 8 f16
+    constexpr int AT_DK = DK, HALF = DK / 2, NP = DK / 32, NF = DK / 16, ND = DK / 32, HO = DK / 16, NKO = (HO + AT_NW - 1) / AT_NW;
+    static_assert(DK % 32 == 0 && DK <= 96, "head dimension");
+    __shared__ uint4 kpl[2][(DK / 8) * AT_TK];                                // [plane][channel octet][key] x 8 f16
     __shared__ __attribute__((aligned(16))) _Float16 vpl[2][AT_DK * AT_VS];   // [plane][channel][key]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
     const int b = blockIdx.y / a.H, h = blockIdx.y - b * a.H;
@@ -62,52 +67,59 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
     const unsigned char* __restrict__ mk = a.mask ? a.mask + (size_t)b * T : nullptr;
     float range_max = 0.f;
 
-    // ---- Q' fragments: lane (l31, hi) holds channels 16 s + 8 hi + j of query l31; channel i < 32 and its partner i + 32 are s and s + 2
+    // ---- Q' fragments: lane (l31, hi) holds channels 16 s + 8 hi + j of query l31; channel i < HALF and its partner i + HALF are s and s + NP
     const int tq = blockIdx.x * AT_TQ + 32 * w + l31;
     const int tqc = tq < T ? tq : T - 1;
-    Frag qh[4], ql[4];
+    Frag qh[NF], ql[NF];
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
+    for (int p = 0; p < NP; ++p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int i = 16 * p + 8 * hi + j;
-            const float x1 = qb[(size_t)i * T + tqc], x2 = qb[(size_t)(i + 32) * T + tqc];
-            const float c = a.cs[(size_t)tqc * 32 + i], s = a.sn[(size_t)tqc * 32 + i];
+            const float x1 = qb[(size_t)i * T + tqc], x2 = qb[(size_t)(i + HALF) * T + tqc];
+            const float c = a.cs[(size_t)tqc * HALF + i], s = a.sn[(size_t)tqc * HALF + i];
             const float r1 = (x1 * c - x2 * s) * 16.f, r2 = (x2 * c + x1 * s) * 16.f;
             range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1), __builtin_fabsf(r2)));
             _Float16 hh, ll;
             split_f16(r1, hh, ll);
             qh[p].h[j] = hh; ql[p].h[j] = ll;
             split_f16(r2, hh, ll);
-            qh[p + 2].h[j] = hh; ql[p + 2].h[j] = ll;
+            qh[p + NP].h[j] = hh; ql[p + NP].h[j] = ll;
         }
     }
 
-    // ---- the staged tile: thread (key = lane, wave w) takes K channels 8 w .. 8 w + 7 with their partners (two whole octets after the
-    // rotation) and V channels w, w + 4, ...
-    float kr[16], vr[16];
-    float4 cr[2], sr[2];
+    // ---- the staged tile: thread (key = lane, wave w) takes K channels 8 o .. 8 o + 7 of its octets o = w + 4 n with their partners (two
+    // whole octets after the rotation) and V channels w, w + 4, ...
+    float kr[NKO][16], vr[DK / 4];
+    float4 cr[NKO][2], sr[NKO][2];
     bool valid;
+    // octet w + 4 n exists: known at compile time where every wave has one
+    auto has_octet = [&](int n) { return 4 * n + AT_NW - 1 < HO || 4 * n + w < HO; };
     auto load_tile = [&](int tk0) {
         const int tk = tk0 + lane;
         const int tkc = tk < T ? tk : T - 1;
         valid = tk < T && (!mk || mk[tkc] != 0);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            kr[j] = kb[(size_t)(8 * w + j) * T + tkc];
-            kr[8 + j] = kb[(size_t)(8 * w + j + 32) * T + tkc];
-        }
-        const float4* cp = reinterpret_cast<const float4*>(a.cs + (size_t)tkc * 32 + 8 * w);
-        const float4* sp = reinterpret_cast<const float4*>(a.sn + (size_t)tkc * 32 + 8 * w);
-        cr[0] = cp[0]; cr[1] = cp[1];
-        sr[0] = sp[0]; sr[1] = sp[1];
+        for (int n = 0; n < NKO; ++n) {
+            if (!has_octet(n)) continue;
+            const int o = w + 4 * n;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) vr[i] = vb[(size_t)(w + 4 * i) * T + tkc];
+            for (int j = 0; j < 8; ++j) {
+                kr[n][j] = kb[(size_t)(8 * o + j) * T + tkc];
+                kr[n][8 + j] = kb[(size_t)(8 * o + j + HALF) * T + tkc];
+            }
+            const float4* cp = reinterpret_cast<const float4*>(a.cs + (size_t)tkc * HALF + 8 * o);
+            const float4* sp = reinterpret_cast<const float4*>(a.sn + (size_t)tkc * HALF + 8 * o);
+            cr[n][0] = cp[0]; cr[n][1] = cp[1];
+            sr[n][0] = sp[0]; sr[n][1] = sp[1];
+        }
+#pragma unroll
+        for (int i = 0; i < DK / 4; ++i) vr[i] = vb[(size_t)(w + 4 * i) * T + tkc];
     };
 
-    f32x16 O[2][1];
+    f32x16 O[ND][1];
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < ND; ++db)
 #pragma unroll
         for (int r = 0; r < 16; ++r) O[db][0][r] = 0.f;
     float m = -INFINITY, l = 0.f;
@@ -117,13 +129,16 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
     load_tile(0);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
-        {
-            const float cc[8] = {cr[0].x, cr[0].y, cr[0].z, cr[0].w, cr[1].x, cr[1].y, cr[1].z, cr[1].w};
-            const float ss[8] = {sr[0].x, sr[0].y, sr[0].z, sr[0].w, sr[1].x, sr[1].y, sr[1].z, sr[1].w};
+#pragma unroll
+        for (int n = 0; n < NKO; ++n) {
+            if (!has_octet(n)) continue;
+            const int o = w + 4 * n;
+            const float cc[8] = {cr[n][0].x, cr[n][0].y, cr[n][0].z, cr[n][0].w, cr[n][1].x, cr[n][1].y, cr[n][1].z, cr[n][1].w};
+            const float ss[8] = {sr[n][0].x, sr[n][0].y, sr[n][0].z, sr[n][0].w, sr[n][1].x, sr[n][1].y, sr[n][1].z, sr[n][1].w};
             float r1[8], r2[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float u1 = (kr[j] * cc[j] - kr[8 + j] * ss[j]) * 16.f, u2 = (kr[8 + j] * cc[j] + kr[j] * ss[j]) * 16.f;
+                const float u1 = (kr[n][j] * cc[j] - kr[n][8 + j] * ss[j]) * 16.f, u2 = (kr[n][8 + j] * cc[j] + kr[n][j] * ss[j]) * 16.f;
                 r1[j] = valid ? u1 : 0.f;
                 r2[j] = valid ? u2 : 0.f;
                 range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1[j]), __builtin_fabsf(r2[j])));
@@ -131,14 +146,16 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
             uint2 h0, l0, h1, l1;
             split4_f16(amp_f32x2{r1[0], r1[1]}, amp_f32x2{r1[2], r1[3]}, h0, l0);
             split4_f16(amp_f32x2{r1[4], r1[5]}, amp_f32x2{r1[6], r1[7]}, h1, l1);
-            kpl[0][w * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
-            kpl[1][w * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+            kpl[0][o * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
+            kpl[1][o * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
             split4_f16(amp_f32x2{r2[0], r2[1]}, amp_f32x2{r2[2], r2[3]}, h0, l0);
             split4_f16(amp_f32x2{r2[4], r2[5]}, amp_f32x2{r2[6], r2[7]}, h1, l1);
-            kpl[0][(w + 4) * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
-            kpl[1][(w + 4) * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+            kpl[0][(o + HO) * AT_TK + lane] = make_uint4(h0.x, h0.y, h1.x, h1.y);
+            kpl[1][(o + HO) * AT_TK + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        }
+        {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
+            for (int i = 0; i < DK / 4; ++i) {
                 const float u = valid ? vr[i] * 16.f : 0.f;
                 range_max = __builtin_fmaxf(range_max, __builtin_fabsf(u));
                 _Float16 hh, ll;
@@ -151,14 +168,14 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
         __syncthreads();
         if (kt + 1 < nkt) load_tile((kt + 1) * AT_TK);     // in flight behind the products below
 
-        // ---- S^T = K'^T Q' over the 64 channels
+        // ---- S^T = K'^T Q' over the DK channels
         f32x16 S[2][1];
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) S[rb][0][r] = 0.f;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
+        for (int s = 0; s < NF; ++s) {
             Frag ah[2], al[2];
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
@@ -190,7 +207,7 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
             const float alpha = __builtin_amdgcn_exp2f((m - m_use) * LOG2E);
             l *= alpha;
 #pragma unroll
-            for (int db = 0; db < 2; ++db)
+            for (int db = 0; db < ND; ++db)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) O[db][0][r] *= alpha;
             m = m_new;
@@ -213,16 +230,16 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
         // ---- O += V P^T: chunk c's k-slot (hi, j) is key 16 c + 8 (j >> 2) + 4 hi + (j & 3)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            Frag vh[2], vl[2];
+            Frag vh[ND], vl[ND];
 #pragma unroll
-            for (int db = 0; db < 2; ++db) {
+            for (int db = 0; db < ND; ++db) {
                 const int off = (32 * db + l31) * AT_VS + 16 * c + 4 * hi;
                 const uint2 x0 = *reinterpret_cast<const uint2*>(&vpl[0][off]), x1 = *reinterpret_cast<const uint2*>(&vpl[0][off + 8]);
                 const uint2 y0 = *reinterpret_cast<const uint2*>(&vpl[1][off]), y1 = *reinterpret_cast<const uint2*>(&vpl[1][off + 8]);
                 vh[db].u = make_uint4(x0.x, x0.y, x1.x, x1.y);
                 vl[db].u = make_uint4(y0.x, y0.y, y1.x, y1.y);
             }
-            mfma3_tiles<2, 1>(O, vh, vl, &ph[c], &pl[c]);
+            mfma3_tiles<ND, 1>(O, vh, vl, &ph[c], &pl[c]);
         }
     }
 
@@ -231,7 +248,7 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
     if (tq < T) {
         float* ob = a.out + ((size_t)blockIdx.y * AT_DK) * T + tq;
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+        for (int db = 0; db < ND; ++db)
 #pragma unroll
             for (int r = 0; r < 16; ++r) ob[(size_t)acc_row(r, hi, 32 * db) * T] = O[db][0][r] * inv;
     }
@@ -331,7 +348,7 @@ int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_de
                        const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
                        void* stream) {
     if (!q_dev || !k_dev || !v_dev || !cos_dev || !sin_dev || !out_dev) { set_error("amp_rope_attention: null argument"); return AMP_ERR_INVALID; }
-    if (dk != AT_DK) { set_error("amp_rope_attention: head dimension %d is not covered (dk = %d only)", dk, AT_DK); return AMP_ERR_INVALID; }
+    if (dk != 64 && dk != 96) { set_error("amp_rope_attention: head dimension %d is not covered (dk = 64 or 96)", dk); return AMP_ERR_INVALID; }
     if (B < 1 || H < 1 || T < 1) { set_error("amp_rope_attention: B=%d H=%d T=%d", B, H, T); return AMP_ERR_INVALID; }
     if (T > AT_MAX_T) { set_error("amp_rope_attention: T=%d is beyond %d", T, AT_MAX_T); return AMP_ERR_INVALID; }
     if ((long long)B * H > 65535) { set_error("amp_rope_attention: B*H=%lld is beyond the grid (65535)", (long long)B * H); return AMP_ERR_INVALID; }
@@ -365,10 +382,11 @@ int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_de
     a.c = scale * (1.0f / 256.f);
     a.range_flag = range_flag_for_current_device();
     const dim3 grid((unsigned)((T + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
-    note_kernel("rope_attention_kernel");
+    note_kernel("rope_attention_kernel", dk);
     note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
               "rope attention B=%d H=%d dk=%d T=%d mask=%d", B, H, dk, T, key_mask_dev ? 1 : 0);
-    hipLaunchKernelGGL(rope_attention_kernel, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+    if (dk == 64) hipLaunchKernelGGL(rope_attention_kernel<64>, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(rope_attention_kernel<96>, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
     AMP_HIP(hipGetLastError());
     return AMP_OK;
 }

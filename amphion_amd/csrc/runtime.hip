@@ -199,7 +199,8 @@ extern "C" {
 // 151 (additive): amp_set_strip_fit and amp_pair_strip_plan (fitted strips of the fused-pair strip kernel, conv_host.hip strip_geometry);
 // 152 (additive): FACodec voice conversion's amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (vits_text.hip);
 // 153 (additive): the flow-matching transformer's amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (llama_nar.hip)
-int amp_version(void) { return 153; }
+// 154 (additive): amp_mask_sample (maskgct.hip); amp_rope_attention at head dimension 96
+int amp_version(void) { return 154; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

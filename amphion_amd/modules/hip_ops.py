@@ -501,7 +501,7 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
 
     q, k, v [B, H*dk, T] channel-first: contiguous tensors, or the three row blocks of one stacked [B, 3*H*dk, T] GEMM output (read in
     place: no copy).  cos, sin [T, dk/2] (``rope_tables``).  key_mask [B, T] bool / uint8, 1 = valid, any pattern, at least one valid key
-    per item; None = all valid.  -> [B, H*dk, T].  dk = 64.  Under the "f32" precision the same formula runs as RoPE in torch plus
+    per item; None = all valid.  -> [B, H*dk, T].  dk = 64 or 96.  Under the "f32" precision the same formula runs as RoPE in torch plus
     ``scaled_dot_product_attention`` (not the hot path)."""
     for t, name in ((q, "q"), (k, "k"), (v, "v"), (cos, "cos"), (sin, "sin")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
@@ -514,8 +514,8 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
     if H < 1 or C % H:
         raise ValueError(f"rope_attention: {C} channels do not divide into {H} heads")
     dk = C // H
-    if dk != 64:
-        raise ValueError(f"rope_attention: head dimension {dk} is not covered (dk = 64 only)")
+    if dk not in (64, 96):
+        raise ValueError(f"rope_attention: head dimension {dk} is not covered (dk = 64 or 96)")
     if B < 1 or T < 1:
         raise ValueError(f"rope_attention: empty input {tuple(q.shape)}")
     if tuple(cos.shape) != (T, dk // 2) or tuple(sin.shape) != (T, dk // 2) or cos.device != q.device or sin.device != q.device:
@@ -545,3 +545,36 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
         _lib.check(_lib.lib().amp_rope_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), _ptr(key_mask), B, H, dk, T, scale,
                                                  _ptr(out), _stream(q)))
     return out
+
+
+# ---- MaskGCT's decoding step (csrc/maskgct.hip) ----------------
+def mask_sample(logits, k, u=None, temperature=1.0):
+    """One decoding step's sampler (``amp_mask_sample``; maskgct_t2s.py: ``top_k``, ``gumbel_sample``, ``softmax().gather()``).
+
+    logits [B, V, T] channel-first, the pointwise GEMM's output: contiguous, or a row block of a wider tensor (read in place through its
+    batch stride).  k: how many of a frame's largest logits stay, ``ceil((1 - filter_thres) * V)``.  u [B, T, V] uniform noise in the
+    reference's own shape, or None for the greedy step (``temperature`` is then ignored).
+    -> (ids [B, T] int64, score [B, T]): the argmax over the kept entries of ``l / max(temperature, 1e-10) - log(-log(u + 1e-10) + 1e-10)``
+    and the softmax of the filtered logits (temperature 1) at that id.  Ties go to the lower index.  2 <= V <= 8192."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.dtype != torch.float32:
+        raise TypeError("mask_sample: logits must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
+    if logits.dim() != 3 or logits.numel() == 0:
+        raise ValueError(f"mask_sample: expected non-empty [B, V, T] logits, got {tuple(logits.shape)}")
+    B, V, T = logits.shape
+    k = int(k)
+    if not 2 <= V <= 8192 or not 1 <= k <= V:
+        raise ValueError(f"mask_sample: V={V} (2..8192), k={k} (1..V)")
+    bstride = logits.stride(0) if B > 1 else max(logits.stride(0), V * T)
+    if not _rows_view(logits, V, T, bstride) or bstride < V * T:
+        logits = logits.contiguous()
+        bstride = V * T
+    if u is not None:
+        if not isinstance(u, torch.Tensor) or u.device != logits.device or u.dtype != torch.float32 or tuple(u.shape) != (B, T, V):
+            raise ValueError(f"mask_sample: u must be a float32 {(B, T, V)} tensor on {logits.device}")
+        u = u.contiguous()
+    ids = torch.empty((B, T), dtype=torch.int64, device=logits.device)
+    score = torch.empty((B, T), dtype=torch.float32, device=logits.device)
+    with _lib.on_device(logits.device):
+        _lib.check(_lib.lib().amp_mask_sample(_ptr(logits), int(bstride), B, V, T, k, _ptr(u), float(temperature), _ptr(ids), _ptr(score),
+                                              _stream(logits)))
+    return ids, score

@@ -100,7 +100,8 @@ typedef struct amp_gen amp_gen;
  * residual unit amp_aa_unit_* and amp_set_aa_unit_fusion; 149 (additive): SpeechTokenizer's amp_elu_pad, amp_lstm_* and amp_evq_*;
  * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan;
  * 152 (additive): amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (FACodec voice conversion);
- * 153 (additive): amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (the flow-matching transformer of Vevo). */
+ * 153 (additive): amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (the flow-matching transformer of Vevo);
+ * 154 (additive): amp_mask_sample (MaskGCT's decoding step), and amp_rope_attention accepts head dimension 96 beside 64. */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -902,7 +903,7 @@ int amp_gelu(const float* x_dev, long long n, float* y_dev, void* stream);
  * route of the drop-in modules is RoPE in torch + scaled_dot_product_attention; the softmax is an online fp32 softmax.  rope(q), rope(k) and v
  * are staged after an exact x16 and take part in the op-level range guard (amp_range_check; masked keys do not).
  * T = 1 is not a launch of the kernel: the softmax over one key is exactly 1, so out is a strided copy of v (its bits, no range guard).
- * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk != 64, B, H or T < 1, T > 32768, B*H > 65535, batch_stride below
+ * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk other than 64 or 96, B, H or T < 1, T > 32768, B*H > 65535, batch_stride below
  * H*dk*T, a misaligned cos / sin, out overlapping q / k / v. */
 int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
                        const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
@@ -922,6 +923,25 @@ int amp_silu(const float* x_dev, long long n, float* y_dev, void* stream);
  * up in rows [F, 2F) -> y[b, f, t] = silu(gu[b, f, t]) * gu[b, F + f, t], y [B, F, T] not overlapping gu.  B <= 65535; bad arguments
  * AMP_ERR_INVALID, more than 2^31 - 1 workgroups per item AMP_ERR_UNSUPPORTED. */
 int amp_swiglu(const float* gu_dev, int B, int F, int T, float* y_dev, void* stream);
+
+/* ---- MaskGCT's decoding step (csrc/maskgct.hip; models/tts/maskgct/maskgct_t2s.py:14-32 top_k / gumbel_sample, :319-337). ---- */
+
+/* The sampler of one decoding step, per (b, t), in one launch:
+ *     kept  = the k largest logits of the row (top_k; the caller computes k = ceil((1 - filter_thres) * V) as the reference does)
+ *     id    = argmax over the kept v of ( l_v / max(temperature, 1e-10) + g_v ),  g = -logf(-logf(u + 1e-10f) + 1e-10f)
+ *             (u_dev NULL: greedy, id = argmax l_v, temperature ignored)
+ *     score = exp(l_id - max) / sum over the kept of exp(l_v - max)      (the filtered logits' softmax at temperature 1, gathered at id)
+ * logits [B, V, T] channel-first -- the pointwise GEMM's output, read in place: rows T apart, items batch_stride elements apart (0 = dense,
+ * V*T).  u [B, T, V] dense, the reference's own noise tensor (zeros_like(logits).uniform_(0, 1)); it is read for the kept entries only.
+ * ids int64 [B, T], score fp32 [B, T], dense.
+ * Plain fp32, accurate expf / logf, a correctly rounded divide.  Deterministic: no atomics, every reduction in a fixed order.
+ * TIES GO TO THE LOWER INDEX, both among logits equal to the k-th largest (which of them are kept) and among equal noisy values (torch
+ * leaves both unspecified); -0 counts as +0.
+ * Logits are assumed finite.  A NaN logit orders beyond +inf or below -inf by its sign bit: the id stays in [0, V), the score is NaN.
+ * AMP_ERR_INVALID with a message, before any launch: a NULL logits / ids / score, V outside [2, 8192], k outside [1, V], B or T < 1,
+ * B > 65535, batch_stride below V*T, a NaN temperature beside a noise tensor, ids or score overlapping logits, u or each other. */
+int amp_mask_sample(const float* logits_dev, long long batch_stride, int B, int V, int T, int k, const float* u_dev, float temperature,
+                    long long* ids_dev, float* score_dev, void* stream);
 
 #ifdef __cplusplus
 }
