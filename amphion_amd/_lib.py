@@ -202,6 +202,18 @@ _SIGNATURES = {
     "amp_rope_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                    c_void_p, c_void_p]),
     "amp_mask_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "amp_rope_attention_causal": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                          c_float, c_void_p, c_void_p]),
+    "amp_kv_append": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p]),
+    "amp_attention_decode": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_attention_decode_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "amp_attention_decode_split": (c_int, []),
+    "amp_pw_forward_vec": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_pw_forward_vec_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "amp_ar_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_float, c_int,
+                              ctypes.c_double, c_float, c_void_p]),
     "amp_layer_norm_c":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_layer_norm_c_style": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

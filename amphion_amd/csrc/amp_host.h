@@ -41,6 +41,22 @@ struct amp_conv {
     }
 };
 
+// ---- amp_pw: one nn.Linear along the channel axis (pw_f16x3.hip; the T = 1 form of llama_ar.hip reads the same packed weights) ----------
+struct amp_pw {
+    int cin = 0, cout = 0;
+    int precision = amp::PREC_F16X3;
+    int nsteps = 0;
+    float inv_scale = 1.f;
+    uint4* wp_dev = nullptr;     // f16x3: packed fragments
+    float* bias_dev = nullptr;   // [cout] (zeros when the Linear has no bias)
+    amp_conv* conv = nullptr;    // exact-fp32 mode: the k = 1 conv
+    ~amp_pw() {
+        if (wp_dev) (void)hipFree(wp_dev);
+        if (bias_dev) (void)hipFree(bias_dev);
+        delete conv;
+    }
+};
+
 namespace amp {
 
 // hipMalloc + hipMemcpy of `bytes` host bytes; on success the caller owns *out (hipFree), on failure nothing is left allocated

@@ -1,6 +1,7 @@
 // The kernels of the non-autoregressive Llama of Vevo / MaskGCT (models/vc/flow_matching_transformer/llama_nar.py: DiffLlama), the parts
 // the pointwise GEMM (pw_f16x3.hip) does not cover:
 //     amp_rope_attention        non-causal multi-head self-attention with rotary position embedding and a key mask, one launch
+//     amp_rope_attention_causal the same kernel with its compile-time causal flag: the prefill of the autoregressive transformer (llama_ar.hip)
 //     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
 //     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
 // Everything is channel-first [B, C, T] fp32.  Deterministic: no atomics on data (the attention kernel ORs the op-level range flag).
@@ -51,7 +52,10 @@ struct AttnArgs {
 // DK = 64 or 96.  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
 // S, ND = DK / 32 the row blocks of O, HO = DK / 16 the channel octets per half: wave w stages octets w, w + 4, ... < HO with their partners
 // (at DK = 96 waves 0 and 1 take two octet pairs, waves 2 and 3 one).
-template <int DK>
+// CAUSAL (amp_rope_attention_causal): key j is visible to query i iff j <= i (and the key mask admits it).  The workgroup walks the key
+// tiles up to the one that holds its last query; in a tile that reaches beyond the wave's first query the comparison joins the validity
+// select below.  A key beyond the query is staged like any other and meets p = exp2(-inf) = 0: it contributes exactly 0.
+template <int DK, bool CAUSAL>
 __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) {
     constexpr int AT_DK = DK, HALF = DK / 2, NP = DK / 32, NF = DK / 16, ND = DK / 32, HO = DK / 16, NKO = (HO + AT_NW - 1) / AT_NW;
     static_assert(DK % 32 == 0 && DK <= 96, "head dimension");
@@ -125,7 +129,12 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
     float m = -INFINITY, l = 0.f;
     constexpr float LOG2E = 1.4426950408889634f;
 
-    const int nkt = (T + AT_TK - 1) / AT_TK;
+    int nkt = (T + AT_TK - 1) / AT_TK;
+    if (CAUSAL) {                                          // uniform over the workgroup: the tile of its last query
+        const int qlast = (int)blockIdx.x * AT_TQ + AT_TQ - 1;
+        nkt = (qlast < T ? qlast : T - 1) / AT_TK + 1;
+    }
+    const int qw0 = (int)blockIdx.x * AT_TQ + 32 * w;      // the wave's first query
     load_tile(0);
     for (int kt = 0; kt < nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
@@ -189,6 +198,7 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
         float sv[2][16];
         float mx = -INFINITY;
         const bool all_valid = km == ~0ull;
+        const bool diag = CAUSAL && kt * AT_TK + AT_TK - 1 > qw0;      // uniform over the wave: some key of the tile is beyond some query
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
             const unsigned mw = (unsigned)(km >> (32 * rb)) >> (4 * hi);
@@ -196,6 +206,9 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
             for (int r = 0; r < 16; ++r) {
                 float s = S[rb][0][r] * a.c;
                 if (!all_valid) s = ((mw >> acc_row(r)) & 1u) ? s : -INFINITY;
+                if (CAUSAL) {
+                    if (diag) s = acc_row(r, hi, kt * AT_TK + 32 * rb) <= tq ? s : -INFINITY;
+                }
                 sv[rb][r] = s;
                 mx = __builtin_fmaxf(mx, s);
             }
@@ -342,31 +355,30 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ g
 
 using namespace amp;
 
-extern "C" {
-
-int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
-                       const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
-                       void* stream) {
-    if (!q_dev || !k_dev || !v_dev || !cos_dev || !sin_dev || !out_dev) { set_error("amp_rope_attention: null argument"); return AMP_ERR_INVALID; }
-    if (dk != 64 && dk != 96) { set_error("amp_rope_attention: head dimension %d is not covered (dk = 64 or 96)", dk); return AMP_ERR_INVALID; }
-    if (B < 1 || H < 1 || T < 1) { set_error("amp_rope_attention: B=%d H=%d T=%d", B, H, T); return AMP_ERR_INVALID; }
-    if (T > AT_MAX_T) { set_error("amp_rope_attention: T=%d is beyond %d", T, AT_MAX_T); return AMP_ERR_INVALID; }
-    if ((long long)B * H > 65535) { set_error("amp_rope_attention: B*H=%lld is beyond the grid (65535)", (long long)B * H); return AMP_ERR_INVALID; }
-    if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("amp_rope_attention: scale=%g", (double)scale); return AMP_ERR_INVALID; }
+// both attention entries: `who` names the entry in the messages, `causal` picks the instantiation
+static int rope_attention_run(const char* who, bool causal, const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride,
+                              const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale,
+                              float* out_dev, void* stream) {
+    if (!q_dev || !k_dev || !v_dev || !cos_dev || !sin_dev || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
+    if (dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
+    if (B < 1 || H < 1 || T < 1) { set_error("%s: B=%d H=%d T=%d", who, B, H, T); return AMP_ERR_INVALID; }
+    if (T > AT_MAX_T) { set_error("%s: T=%d is beyond %d", who, T, AT_MAX_T); return AMP_ERR_INVALID; }
+    if ((long long)B * H > 65535) { set_error("%s: B*H=%lld is beyond the grid (65535)", who, (long long)B * H); return AMP_ERR_INVALID; }
+    if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("%s: scale=%g", who, (double)scale); return AMP_ERR_INVALID; }
     if (batch_stride == 0) batch_stride = (long long)H * dk * T;
-    if (batch_stride < (long long)H * dk * T) { set_error("amp_rope_attention: batch stride %lld < H*dk*T", batch_stride); return AMP_ERR_INVALID; }
+    if (batch_stride < (long long)H * dk * T) { set_error("%s: batch stride %lld < H*dk*T", who, batch_stride); return AMP_ERR_INVALID; }
     if ((reinterpret_cast<uintptr_t>(cos_dev) | reinterpret_cast<uintptr_t>(sin_dev)) & 15) {
-        set_error("amp_rope_attention: cos / sin must be 16-byte aligned");
+        set_error("%s: cos / sin must be 16-byte aligned", who);
         return AMP_ERR_INVALID;
     }
     const size_t span = (size_t)(B - 1) * (size_t)batch_stride + (size_t)H * dk * T;
     const float* olo = out_dev;
     const float* ohi = out_dev + (size_t)B * H * dk * T;
     for (const float* p : {q_dev, k_dev, v_dev})
-        if (p < ohi && olo < p + span) { set_error("amp_rope_attention: out must not overlap q / k / v"); return AMP_ERR_INVALID; }
+        if (p < ohi && olo < p + span) { set_error("%s: out must not overlap q / k / v", who); return AMP_ERR_INVALID; }
     if (T == 1) {
-        // One key: the softmax over it is exactly 1 whatever q and k hold (the item's one key is valid, see the header), so the attention
-        // is the identity on v and there is no product to form.  A strided copy returns v's bits, as the fp32 reference does (1.0f * v),
+        // One key (query 0 sees key 0 under the causal rule too): the softmax over it is exactly 1 whatever q and k hold (the item's one key
+        // is valid, see the header), so the attention is the identity on v and there is no product to form.  A strided copy returns v's bits, as the fp32 reference does (1.0f * v),
         // where the split-f16 operand of the kernel would return 22 of its 24 mantissa bits.
         AMP_HIP(hipMemcpy2DAsync(out_dev, (size_t)H * dk * sizeof(float), v_dev, (size_t)batch_stride * sizeof(float),
                                  (size_t)H * dk * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -382,13 +394,30 @@ int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_de
     a.c = scale * (1.0f / 256.f);
     a.range_flag = range_flag_for_current_device();
     const dim3 grid((unsigned)((T + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
-    note_kernel("rope_attention_kernel", dk);
-    note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
-              "rope attention B=%d H=%d dk=%d T=%d mask=%d", B, H, dk, T, key_mask_dev ? 1 : 0);
-    if (dk == 64) hipLaunchKernelGGL(rope_attention_kernel<64>, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(rope_attention_kernel<96>, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+    note_kernel("rope_attention_kernel", dk, causal ? 1 : 0);
+    note_work((unsigned long long)grid.x * grid.y, (causal ? 0.5 : 1.0) * 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
+              "rope attention%s B=%d H=%d dk=%d T=%d mask=%d", causal ? " causal" : "", B, H, dk, T, key_mask_dev ? 1 : 0);
+    auto kern = dk == 64 ? (causal ? rope_attention_kernel<64, true> : rope_attention_kernel<64, false>)
+                         : (causal ? rope_attention_kernel<96, true> : rope_attention_kernel<96, false>);
+    hipLaunchKernelGGL(kern, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
     AMP_HIP(hipGetLastError());
     return AMP_OK;
+}
+
+extern "C" {
+
+int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
+                       const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
+                       void* stream) {
+    return rope_attention_run("amp_rope_attention", false, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T, scale,
+                              out_dev, stream);
+}
+
+int amp_rope_attention_causal(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
+                              const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
+                              void* stream) {
+    return rope_attention_run("amp_rope_attention_causal", true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T,
+                              scale, out_dev, stream);
 }
 
 int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,

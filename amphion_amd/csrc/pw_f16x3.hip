@@ -223,21 +223,6 @@ __global__ __launch_bounds__(256) void pw_epilogue_kernel(float* __restrict__ y,
 
 using namespace amp;
 
-struct amp_pw {
-    int cin = 0, cout = 0;
-    int precision = PREC_F16X3;
-    int nsteps = 0;
-    float inv_scale = 1.f;
-    uint4* wp_dev = nullptr;     // f16x3: packed fragments
-    float* bias_dev = nullptr;   // [cout] (zeros when the Linear has no bias)
-    amp_conv* conv = nullptr;    // exact-fp32 mode: the k = 1 conv
-    ~amp_pw() {
-        if (wp_dev) (void)hipFree(wp_dev);
-        if (bias_dev) (void)hipFree(bias_dev);
-        delete conv;
-    }
-};
-
 extern "C" {
 
 int amp_pw_create(int cin, int cout, const float* weight_host, const float* bias_host, amp_pw** out) {

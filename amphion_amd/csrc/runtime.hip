@@ -200,7 +200,9 @@ extern "C" {
 // 152 (additive): FACodec voice conversion's amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (vits_text.hip);
 // 153 (additive): the flow-matching transformer's amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (llama_nar.hip)
 // 154 (additive): amp_mask_sample (maskgct.hip); amp_rope_attention at head dimension 96
-int amp_version(void) { return 154; }
+// 155 (additive): the autoregressive transformer's amp_rope_attention_causal (llama_nar.hip) and amp_kv_append, amp_attention_decode,
+// amp_pw_forward_vec and amp_ar_sample with their workspace queries (llama_ar.hip)
+int amp_version(void) { return 155; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

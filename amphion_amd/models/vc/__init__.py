@@ -1,1 +1,1 @@
-"""Voice-conversion models (models/vc): Vevo's flow-matching transformer."""
+"""Voice-conversion models (models/vc): Vevo's autoregressive transformer and flow-matching transformer."""

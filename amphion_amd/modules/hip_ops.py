@@ -496,13 +496,14 @@ def _rows_view(t, C, T, bstride):
     return t.stride(2) == 1 and (C == 1 or t.stride(1) == T) and (t.shape[0] == 1 or t.stride(0) == bstride)
 
 
-def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
+def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None, causal=False):
     """Non-causal multi-head self-attention with rotary position embedding (HF's rotate-half form) and a KEY mask (``amp_rope_attention``).
 
     q, k, v [B, H*dk, T] channel-first: contiguous tensors, or the three row blocks of one stacked [B, 3*H*dk, T] GEMM output (read in
     place: no copy).  cos, sin [T, dk/2] (``rope_tables``).  key_mask [B, T] bool / uint8, 1 = valid, any pattern, at least one valid key
     per item; None = all valid.  -> [B, H*dk, T].  dk = 64 or 96.  Under the "f32" precision the same formula runs as RoPE in torch plus
-    ``scaled_dot_product_attention`` (not the hot path)."""
+    ``scaled_dot_product_attention`` (not the hot path).  ``causal=True``: key j is visible to query i iff j <= i and the mask admits it
+    (``amp_rope_attention_causal``, the prefill of the autoregressive transformer)."""
     for t, name in ((q, "q"), (k, "k"), (v, "v"), (cos, "cos"), (sin, "sin")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
             raise TypeError(f"rope_attention: {name} must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
@@ -535,6 +536,9 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
                 c, s = torch.cat((cos, cos), -1), torch.cat((sin, sin), -1)
                 return x * c + torch.cat((-x[..., dk // 2:], x[..., : dk // 2]), -1) * s
             m = None if key_mask is None else key_mask.bool()[:, None, None, :]
+            if causal:
+                tri = torch.ones((T, T), dtype=torch.bool, device=q.device).tril()[None, None]
+                m = tri if m is None else m & tri
             o = torch.nn.functional.scaled_dot_product_attention(rope(q), rope(k), v.reshape(B, H, dk, T).transpose(2, 3), attn_mask=m, scale=scale)
             return o.transpose(2, 3).reshape(B, C, T).contiguous()
         bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
@@ -542,8 +546,8 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None):
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
             bstride = C * T
         out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().amp_rope_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), _ptr(key_mask), B, H, dk, T, scale,
-                                                 _ptr(out), _stream(q)))
+        entry = _lib.lib().amp_rope_attention_causal if causal else _lib.lib().amp_rope_attention
+        _lib.check(entry(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), _ptr(key_mask), B, H, dk, T, scale, _ptr(out), _stream(q)))
     return out
 
 
@@ -578,3 +582,141 @@ def mask_sample(logits, k, u=None, temperature=1.0):
         _lib.check(_lib.lib().amp_mask_sample(_ptr(logits), int(bstride), B, V, T, k, _ptr(u), float(temperature), _ptr(ids), _ptr(score),
                                               _stream(logits)))
     return ids, score
+
+
+# ---- the autoregressive transformer's decode step (csrc/llama_ar.hip) ----------------
+def _f32_dev(t, name, who):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
+    return t
+
+
+def kv_cache(B, n_heads, dk, Lmax, device):
+    """one layer's (K, V) cache, two fp32 [B, H*dk, Lmax] buffers (K holds rope(k))"""
+    shape = (int(B), int(n_heads) * int(dk), int(Lmax))
+    return torch.zeros(shape, dtype=torch.float32, device=device), torch.zeros(shape, dtype=torch.float32, device=device)
+
+
+def kv_append(k, v, n_heads, cos, sin, pos0, kcache, vcache):
+    """rope(k) and v of the T columns of k, v [B, H*dk, T] (contiguous, or row blocks of one stacked GEMM output) into columns
+    [pos0, pos0 + T) of the caches [B, H*dk, Lmax] (``amp_kv_append``); cos, sin [>= pos0 + T, dk/2] are the tables from row 0"""
+    for t, name in ((k, "k"), (v, "v"), (cos, "cos"), (sin, "sin"), (kcache, "kcache"), (vcache, "vcache")):
+        _f32_dev(t, name, "kv_append")
+    if k.dim() != 3 or k.shape != v.shape or k.numel() == 0:
+        raise ValueError(f"kv_append: k and v must be non-empty [B, H*dk, T] tensors of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    B, C, T = k.shape
+    H = int(n_heads)
+    if H < 1 or C % H or C // H not in (64, 96):
+        raise ValueError(f"kv_append: {C} channels in {H} heads is not a head dimension of 64 or 96")
+    dk, pos0 = C // H, int(pos0)
+    if kcache.dim() != 3 or kcache.shape != vcache.shape or tuple(kcache.shape[:2]) != (B, C) or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError(f"kv_append: the caches must be contiguous [{B}, {C}, Lmax] tensors, got {tuple(kcache.shape)} and {tuple(vcache.shape)}")
+    Lmax = kcache.shape[2]
+    if pos0 < 0 or pos0 + T > Lmax:
+        raise ValueError(f"kv_append: columns [{pos0}, {pos0 + T}) do not fit a cache of {Lmax}")
+    if cos.dim() != 2 or cos.shape != sin.shape or cos.shape[1] != dk // 2 or cos.shape[0] < pos0 + T:
+        raise ValueError(f"kv_append: cos and sin must be [>= {pos0 + T}, {dk // 2}], got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    cos, sin = cos.contiguous(), sin.contiguous()
+    bstride = k.stride(0) if B > 1 else max(k.stride(0), C * T)
+    if not (_rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
+        k, v = k.contiguous(), v.contiguous()
+        bstride = C * T
+    with _lib.on_device(k.device):
+        _lib.check(_lib.lib().amp_kv_append(_ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), B, H, dk, T, pos0, Lmax, _ptr(kcache), _ptr(vcache),
+                                            _stream(k)))
+
+
+_decode_ws = {}     # (device, bytes) -> workspace
+
+
+def _workspace(device, nbytes):
+    key = (str(device), int(nbytes))
+    t = _decode_ws.get(key)
+    if t is None:
+        if len(_decode_ws) >= 64:
+            _decode_ws.clear()
+        t = _decode_ws[key] = torch.empty(max(1, (int(nbytes) + 3) // 4), dtype=torch.float32, device=device)
+    return t
+
+
+def attention_decode(q, n_heads, cos, sin, L, kcache, vcache, scale=None):
+    """One decode step's attention (``amp_attention_decode``): q [B, H*dk] or [B, H*dk, 1], un-rotated (a row block of the stacked GEMM
+    output is read in place), at position L - 1 over cache columns [0, L) -> [B, H*dk, 1].  cos, sin [>= L, dk/2] from row 0."""
+    for t, name in ((q, "q"), (cos, "cos"), (sin, "sin"), (kcache, "kcache"), (vcache, "vcache")):
+        _f32_dev(t, name, "attention_decode")
+    if q.dim() == 3 and q.shape[2] == 1:
+        q = q[:, :, 0]
+    if q.dim() != 2 or q.numel() == 0:
+        raise ValueError(f"attention_decode: q must be [B, H*dk] or [B, H*dk, 1], got {tuple(q.shape)}")
+    B, C = q.shape
+    H, L = int(n_heads), int(L)
+    if H < 1 or C % H or C // H not in (64, 96):
+        raise ValueError(f"attention_decode: {C} channels in {H} heads is not a head dimension of 64 or 96")
+    dk = C // H
+    if kcache.dim() != 3 or kcache.shape != vcache.shape or tuple(kcache.shape[:2]) != (B, C) or not kcache.is_contiguous() or not vcache.is_contiguous():
+        raise ValueError(f"attention_decode: the caches must be contiguous [{B}, {C}, Lmax] tensors, got {tuple(kcache.shape)} and {tuple(vcache.shape)}")
+    Lmax = kcache.shape[2]
+    if not 1 <= L <= Lmax:
+        raise ValueError(f"attention_decode: L={L} is outside [1, {Lmax}]")
+    if cos.dim() != 2 or cos.shape != sin.shape or cos.shape[1] != dk // 2 or cos.shape[0] < L:
+        raise ValueError(f"attention_decode: cos and sin must be [>= {L}, {dk // 2}], got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    cos, sin = cos.contiguous(), sin.contiguous()
+    if (C > 1 and q.stride(1) != 1) or (B > 1 and q.stride(0) < C):
+        q = q.contiguous()
+    qbs = int(q.stride(0)) if B > 1 else C
+    scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
+    out = torch.empty((B, C, 1), dtype=torch.float32, device=q.device)
+    with _lib.on_device(q.device):
+        L_ = _lib.lib()
+        nbytes = L_.amp_attention_decode_workspace_bytes(B, H, dk, Lmax)
+        ws = _workspace(q.device, nbytes)
+        _lib.check(L_.amp_attention_decode(_ptr(q), qbs, _ptr(cos), _ptr(sin), _ptr(kcache), _ptr(vcache), B, H, dk, L, Lmax, scale, _ptr(out),
+                                           _ptr(ws), nbytes, _stream(q)))
+    return out
+
+
+def pw_forward_vec(h, cout, x, gamma=None, res=None, out=None):
+    """``amp_pw_forward_vec``: the Linear of the ``amp_pw`` handle ``h`` on x [B, cin, 1] (B <= 8; contiguous, or a row block of a wider
+    [B, C, 1] tensor) -> [B, cout, 1]; with ``res`` (and ``gamma`` [cout]) the ``res + gamma * (Wx + b)`` epilogue"""
+    _f32_dev(x, "x", "pw_forward_vec")
+    if x.dim() != 3 or x.shape[2] != 1 or x.numel() == 0:
+        raise ValueError(f"pw_forward_vec: expected a [B, cin, 1] input, got {tuple(x.shape)}")
+    B, cin = x.shape[0], x.shape[1]
+    if (cin > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < cin):
+        x = x.contiguous()
+    xbs = int(x.stride(0)) if B > 1 else cin
+    if out is None:
+        out = torch.empty((B, int(cout), 1), dtype=torch.float32, device=x.device)
+    epi = 0 if res is None else 2
+    with _lib.on_device(x.device):
+        L_ = _lib.lib()
+        nbytes = L_.amp_pw_forward_vec_workspace_bytes(h, B)
+        ws = _workspace(x.device, nbytes)
+        _lib.check(L_.amp_pw_forward_vec(h, _ptr(x), xbs, B, epi, _ptr(gamma), _ptr(res), _ptr(out), _ptr(ws), nbytes, _stream(x)))
+    return out
+
+
+def ar_sample(logits, q, ids, n_ids, eos_id, suppress_eos, temperature=1.0, top_k=50, top_p=1.0, repetition_penalty=1.0):
+    """One decode step's sampler (``amp_ar_sample``): HF's repetition penalty -> EOS suppression -> temperature -> top-k -> top-p chain on
+    logits [B, V] / [B, V, 1] and the race ``argmax p / q`` against the Exp(1) noise q [B, V].  ids [B, capacity] int64 holds the ids so
+    far in columns [0, n_ids) (the penalty's history); the drawn id is written to column n_ids.  Returns ``ids``."""
+    _f32_dev(logits, "logits", "ar_sample")
+    _f32_dev(q, "q", "ar_sample")
+    if logits.dim() == 3 and logits.shape[2] == 1:
+        logits = logits[:, :, 0]
+    if logits.dim() != 2 or logits.numel() == 0:
+        raise ValueError(f"ar_sample: logits must be [B, V] or [B, V, 1], got {tuple(logits.shape)}")
+    B, V = logits.shape
+    if (V > 1 and logits.stride(1) != 1) or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    if tuple(q.shape) != (B, V) or q.device != logits.device:
+        raise ValueError(f"ar_sample: q must be a {(B, V)} tensor on {logits.device}, got {tuple(q.shape)}")
+    q = q.contiguous()
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != logits.device or ids.dim() != 2 or ids.shape[0] != B \
+            or not ids.is_contiguous():
+        raise ValueError(f"ar_sample: ids must be a contiguous int64 [{B}, capacity] tensor on {logits.device}")
+    with _lib.on_device(logits.device):
+        _lib.check(_lib.lib().amp_ar_sample(_ptr(logits), int(logits.stride(0)) if B > 1 else V, B, V, _ptr(q), _ptr(ids), ids.shape[1], int(n_ids),
+                                            int(eos_id), 1 if suppress_eos else 0, float(temperature), int(top_k), float(top_p),
+                                            float(repetition_penalty), _stream(logits)))
+    return ids

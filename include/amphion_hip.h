@@ -101,7 +101,9 @@ typedef struct amp_gen amp_gen;
  * 150 (additive): the semantic tokenizers' amp_dsconv_* and amp_gelu; 151 (additive): amp_set_strip_fit and amp_pair_strip_plan;
  * 152 (additive): amp_layer_norm_c_style, amp_embed_sum_c and amp_embed_sum_check (FACodec voice conversion);
  * 153 (additive): amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (the flow-matching transformer of Vevo);
- * 154 (additive): amp_mask_sample (MaskGCT's decoding step), and amp_rope_attention accepts head dimension 96 beside 64. */
+ * 154 (additive): amp_mask_sample (MaskGCT's decoding step), and amp_rope_attention accepts head dimension 96 beside 64;
+ * 155 (additive): amp_rope_attention_causal, amp_kv_append, amp_attention_decode (+ _workspace_bytes, _split), amp_pw_forward_vec
+ * (+ _workspace_bytes) and amp_ar_sample (the autoregressive transformer of Vevo). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -942,6 +944,82 @@ int amp_swiglu(const float* gu_dev, int B, int F, int T, float* y_dev, void* str
  * B > 65535, batch_stride below V*T, a NaN temperature beside a noise tensor, ids or score overlapping logits, u or each other. */
 int amp_mask_sample(const float* logits_dev, long long batch_stride, int B, int V, int T, int k, const float* u_dev, float temperature,
                     long long* ids_dev, float* score_dev, void* stream);
+
+/* ---- Vevo's autoregressive transformer (csrc/llama_ar.hip; models/vc/autoregressive_transformer/ar_model.py: a causal LlamaForCausalLM
+ * that decodes one token at a time).  Deterministic, no allocation and no synchronisation; every argument is judged on the host before
+ * anything is launched.  The prefill is amp_pw_forward + amp_rope_attention_causal; a decode step has ONE column per item. ---- */
+
+/* amp_rope_attention under the causal rule: key j is visible to query i iff j <= i AND the key mask admits it.  Same arguments, arithmetic,
+ * range guard, refusals and T = 1 copy as amp_rope_attention (the same kernel with a compile-time flag: a query block walks the key tiles
+ * up to its diagonal tile only).  Columns beyond a query never influence its output column: a hidden key meets p = 0 exactly, whatever
+ * finite value it holds.  A query without a visible valid key (key 0 masked, query 0) gets a NaN column; right-padded batches have none. */
+int amp_rope_attention_causal(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
+                              const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
+                              void* stream);
+
+/* The KV cache of one layer is two fp32 buffers [B, H*dk, Lmax], channel-first like everything here; K is stored ALREADY ROTATED.
+ * amp_kv_append takes T columns of un-rotated k and of v ([B, H*dk, T], rows T apart, one batch stride, 0 = dense: two row blocks of the
+ * stacked q | k | v GEMM output are read in place) at positions pos0 .. pos0 + T - 1 and writes rope(k) (rotate-half, the formula of
+ * amp_rope_attention, fp32) and the BITS of v into columns [pos0, pos0 + T) of the caches.  cos, sin: the tables' row 0, [>= pos0 + T, dk/2].
+ * Once after the prefill with T = the prompt length, then once per step with T = 1.
+ * AMP_ERR_INVALID with a message: a NULL pointer, dk other than 64 or 96, B, H or T < 1, B*H > 65535, pos0 < 0, pos0 + T > Lmax, batch_stride
+ * below H*dk*T, caches overlapping each other or k / v. */
+int amp_kv_append(const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev, const float* sin_dev, int B, int H,
+                  int dk, int T, int pos0, int Lmax, float* kcache_dev, float* vcache_dev, void* stream);
+
+/* One decode step's attention: each (item, head) has ONE query, rotated inside the kernel with row L - 1 of cos / sin (the tables' row 0 is
+ * passed), over cache columns [0, L):
+ *     out[b, h*dk + d] = sum_{s < L} softmax_s( scale * <rope(q)[b, h, :], kcache[b, h, :, s]> ) vcache[b, h*dk + d, s]
+ * q [B, H*dk] with items q_batch_stride elements apart (0 = dense; the first row block of a stacked [B, 3*H*dk, 1] GEMM output is read in
+ * place), out [B, H*dk] dense.  Exact fp32 on the vector pipe (accurate expf, correctly rounded divide), whatever amp_set_precision says.
+ * The keys are split over workgroups of amp_attention_decode_split() keys each; with more than one split the (max, sum, O) partials go
+ * through the workspace (amp_attention_decode_workspace_bytes(B, H, dk, Lmax) bytes serve every L <= Lmax; L <= the split needs none) and a
+ * second small launch adds them in ascending order.  Cache columns >= L are never operands: whatever they hold (NaN, 1e30) leaves the
+ * result's bits alone.
+ * AMP_ERR_INVALID with a message: a NULL pointer (the workspace excepted where none is needed), dk other than 64 or 96, B or H < 1,
+ * B*H > 65535, L < 1, L > Lmax, a non-positive or non-finite scale, q_batch_stride below H*dk, a workspace too small, out or the workspace
+ * overlapping q, the caches or each other. */
+int amp_attention_decode(const float* q_dev, long long q_batch_stride, const float* cos_dev, const float* sin_dev, const float* kcache_dev,
+                         const float* vcache_dev, int B, int H, int dk, int L, int Lmax, float scale, float* out_dev, float* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+size_t amp_attention_decode_workspace_bytes(int B, int H, int dk, int Lmax);
+int amp_attention_decode_split(void);
+
+/* amp_pw_forward at T = 1 for B <= 8 items, on the same handle and from the same packed weights (no second device copy), as a
+ * weight-streaming matrix-vector product: x [B, cin] with items x_batch_stride apart (0 = dense), y [B, cout] dense,
+ *     AMP_PW_BIAS: y = Wx + b        AMP_PW_SCALE_RES: y = res + gamma (.) (Wx + b)   (res [B, cout]; y may alias res)
+ * Every weight is read once, in 16-byte loads, and multiplied in fp32 (an f16x3 handle's weight is hi + lo, exactly the fp32 value the
+ * two planes hold: about 22 of the 24 mantissa bits of the original; an exact-fp32 handle's is the weight itself); x is never split, so
+ * there is no range guard.  Row blocks and K slices spread the matrix over more workgroups than the chip has CUs; the K slices' partial
+ * sums go through the workspace (amp_pw_forward_vec_workspace_bytes(handle, B) bytes) and a second small launch adds them in ascending
+ * order and applies the epilogue.  The order of every sum depends on the shape alone.
+ * AMP_ERR_INVALID with a message: a NULL handle / x / y / workspace, B outside [1, 8], an epilogue other than the two above, AMP_PW_SCALE_RES
+ * without gamma and res, x_batch_stride below cin, a workspace too small, x, y and the workspace overlapping, res overlapping y without
+ * being y. */
+int amp_pw_forward_vec(const amp_pw* h, const float* x_dev, long long x_batch_stride, int B, int epilogue, const float* gamma_dev,
+                       const float* res_dev, float* y_dev, float* workspace_dev, size_t workspace_bytes, void* stream);
+size_t amp_pw_forward_vec_workspace_bytes(const amp_pw* h, int B);
+
+/* One decode step's sampler, one launch, one logits row per item: HF's processor chain as `generate(do_sample=True)` composes it
+ * (transformers/generation/logits_process.py) and the draw.
+ *   1. repetition penalty over the ids seen so far, ids[b, 0 .. n_ids): l < 0 ? l * p : l / p, once per distinct id; skipped at p = 1
+ *   2. suppress_eos != 0: the logit of eos_id becomes -inf (the caller sets it while fewer than min_new_tokens have been generated)
+ *   3. l / temperature
+ *   4. top-k: every logit not below the k-th largest stays -- HF removes l < the k-th value, so ALL ties at the boundary are kept (unlike
+ *      amp_mask_sample); top_k > V keeps everything
+ *   5. top-p: with p1 the softmax of what is left, HF removes the ascending-sorted prefix whose cumulative p1 is <= 1 - top_p, i.e. the
+ *      values whose mass sum{p1_u : l_u <= l_v} is <= 1 - top_p (1 - top_p formed in double, compared in fp32); the maximum always stays;
+ *      top_p >= 1 disables the filter
+ *   6. p = softmax of what is left; id = argmax_v p_v / q_v with q [B, V] the caller's Exp(1) noise -- the exponential race that
+ *      torch.multinomial runs; an equal quotient goes to the LOWER index
+ * The id is written as int64 to ids[b, n_ids]: ids [B, ids_capacity] int64 is both the history of the penalty and the token buffer.
+ * logits [B, V] with items batch_stride apart (0 = dense), read in place from the lm_head output.  2 <= V <= 16384.
+ * Plain fp32, accurate expf, correctly rounded divides, every reduction in a fixed order.  Logits and noise are assumed finite, q > 0.
+ * AMP_ERR_INVALID with a message: a NULL logits / q / ids, V outside [2, 16384], B outside [1, 65535], top_k < 1, top_p <= 0 or NaN, a
+ * temperature or penalty that is not positive and finite, n_ids < 0 or >= ids_capacity, suppress_eos with eos_id outside [0, V),
+ * batch_stride below V, ids overlapping logits or q. */
+int amp_ar_sample(const float* logits_dev, long long batch_stride, int B, int V, const float* q_dev, long long* ids_dev, long long ids_capacity,
+                  int n_ids, int eos_id, int suppress_eos, float temperature, int top_k, double top_p, float repetition_penalty, void* stream);
 
 #ifdef __cplusplus
 }
