@@ -214,6 +214,10 @@ _SIGNATURES = {
     "amp_pw_forward_vec_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "amp_ar_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_float, c_int,
                               ctypes.c_double, c_float, c_void_p]),
+    "amp_mh_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "amp_fs2_durations": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "amp_bucketize_embed_add": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "amp_layer_norm_c_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_layer_norm_c":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
     "amp_layer_norm_c_style": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_add_channel_bias": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

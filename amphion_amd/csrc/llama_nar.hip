@@ -2,6 +2,7 @@
 // the pointwise GEMM (pw_f16x3.hip) does not cover:
 //     amp_rope_attention        non-causal multi-head self-attention with rotary position embedding and a key mask, one launch
 //     amp_rope_attention_causal the same kernel with its compile-time causal flag: the prefill of the autoregressive transformer (llama_ar.hip)
+//     amp_mh_attention          the same kernel with its compile-time rotation flag off, head dimension 128: the FFT block of FastSpeech2 / JETS
 //     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
 //     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
 // Everything is channel-first [B, C, T] fp32.  Deterministic: no atomics on data (the attention kernel ORs the op-level range flag).
@@ -49,18 +50,34 @@ struct AttnArgs {
     unsigned* range_flag;
 };
 
-// DK = 64 or 96.  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
+// DK = 64 or 96 (with rotation), 128 (without).  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
 // S, ND = DK / 32 the row blocks of O, HO = DK / 16 the channel octets per half: wave w stages octets w, w + 4, ... < HO with their partners
 // (at DK = 96 waves 0 and 1 take two octet pairs, waves 2 and 3 one).
 // CAUSAL (amp_rope_attention_causal): key j is visible to query i iff j <= i (and the key mask admits it).  The workgroup walks the key
 // tiles up to the one that holds its last query; in a tile that reaches beyond the wave's first query the comparison joins the validity
 // select below.  A key beyond the query is staged like any other and meets p = exp2(-inf) = 0: it contributes exactly 0.
-template <int DK, bool CAUSAL>
+// ROPE = false (amp_mh_attention, fastspeech.hip's FFT block): no rotation -- Q' = q and K' = k, cs / sn are never read; the channel pairs
+// (i, i + HALF) stay the staging pattern, nothing more.  DK = 128 is built in this form only: its planes (32 KB of K', 34 KB of V) are
+// beyond what a static __shared__ array may hold, so they are the launch's dynamic LDS (attn_lds_bytes); DK <= 96 keeps the static arrays.
+template <int DK>
+constexpr size_t attn_lds_bytes() { return 2 * (size_t)(DK / 8) * AT_TK * sizeof(uint4) + 2 * (size_t)DK * AT_VS * sizeof(_Float16); }
+
+template <int DK, bool CAUSAL, bool ROPE = true>
 __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) {
     constexpr int AT_DK = DK, HALF = DK / 2, NP = DK / 32, NF = DK / 16, ND = DK / 32, HO = DK / 16, NKO = (HO + AT_NW - 1) / AT_NW;
-    static_assert(DK % 32 == 0 && DK <= 96, "head dimension");
-    __shared__ uint4 kpl[2][(DK / 8) * AT_TK];                                // [plane][channel octet][key] x 8 f16
-    __shared__ __attribute__((aligned(16))) _Float16 vpl[2][AT_DK * AT_VS];   // [plane][channel][key]
+    constexpr int KPL = (DK / 8) * AT_TK, VPL = AT_DK * AT_VS;
+    static_assert(DK % 32 == 0 && DK <= 128, "head dimension");
+    uint4 (*kpl)[KPL];                                                        // [plane][channel octet][key] x 8 f16
+    _Float16 (*vpl)[VPL];                                                     // [plane][channel][key]
+    if constexpr (DK <= 96) {
+        __shared__ uint4 kpl_s[2][KPL];
+        __shared__ __attribute__((aligned(16))) _Float16 vpl_s[2][VPL];
+        kpl = kpl_s; vpl = vpl_s;
+    } else {
+        extern __shared__ uint4 attn_dyn[];
+        kpl = reinterpret_cast<uint4 (*)[KPL]>(attn_dyn);
+        vpl = reinterpret_cast<_Float16 (*)[VPL]>(attn_dyn + 2 * KPL);
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
     const int b = blockIdx.y / a.H, h = blockIdx.y - b * a.H;
     const int T = a.T;
@@ -81,8 +98,13 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
         for (int j = 0; j < 8; ++j) {
             const int i = 16 * p + 8 * hi + j;
             const float x1 = qb[(size_t)i * T + tqc], x2 = qb[(size_t)(i + HALF) * T + tqc];
-            const float c = a.cs[(size_t)tqc * HALF + i], s = a.sn[(size_t)tqc * HALF + i];
-            const float r1 = (x1 * c - x2 * s) * 16.f, r2 = (x2 * c + x1 * s) * 16.f;
+            float r1, r2;
+            if constexpr (ROPE) {
+                const float c = a.cs[(size_t)tqc * HALF + i], s = a.sn[(size_t)tqc * HALF + i];
+                r1 = (x1 * c - x2 * s) * 16.f; r2 = (x2 * c + x1 * s) * 16.f;
+            } else {
+                r1 = x1 * 16.f; r2 = x2 * 16.f;
+            }
             range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1), __builtin_fabsf(r2)));
             _Float16 hh, ll;
             split_f16(r1, hh, ll);
@@ -112,10 +134,12 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
                 kr[n][j] = kb[(size_t)(8 * o + j) * T + tkc];
                 kr[n][8 + j] = kb[(size_t)(8 * o + j + HALF) * T + tkc];
             }
-            const float4* cp = reinterpret_cast<const float4*>(a.cs + (size_t)tkc * HALF + 8 * o);
-            const float4* sp = reinterpret_cast<const float4*>(a.sn + (size_t)tkc * HALF + 8 * o);
-            cr[n][0] = cp[0]; cr[n][1] = cp[1];
-            sr[n][0] = sp[0]; sr[n][1] = sp[1];
+            if constexpr (ROPE) {
+                const float4* cp = reinterpret_cast<const float4*>(a.cs + (size_t)tkc * HALF + 8 * o);
+                const float4* sp = reinterpret_cast<const float4*>(a.sn + (size_t)tkc * HALF + 8 * o);
+                cr[n][0] = cp[0]; cr[n][1] = cp[1];
+                sr[n][0] = sp[0]; sr[n][1] = sp[1];
+            }
         }
 #pragma unroll
         for (int i = 0; i < DK / 4; ++i) vr[i] = vb[(size_t)(w + 4 * i) * T + tkc];
@@ -142,12 +166,22 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
         for (int n = 0; n < NKO; ++n) {
             if (!has_octet(n)) continue;
             const int o = w + 4 * n;
-            const float cc[8] = {cr[n][0].x, cr[n][0].y, cr[n][0].z, cr[n][0].w, cr[n][1].x, cr[n][1].y, cr[n][1].z, cr[n][1].w};
-            const float ss[8] = {sr[n][0].x, sr[n][0].y, sr[n][0].z, sr[n][0].w, sr[n][1].x, sr[n][1].y, sr[n][1].z, sr[n][1].w};
+            float cc[8], ss[8];
+            if constexpr (ROPE) {
+                const float c8[8] = {cr[n][0].x, cr[n][0].y, cr[n][0].z, cr[n][0].w, cr[n][1].x, cr[n][1].y, cr[n][1].z, cr[n][1].w};
+                const float s8[8] = {sr[n][0].x, sr[n][0].y, sr[n][0].z, sr[n][0].w, sr[n][1].x, sr[n][1].y, sr[n][1].z, sr[n][1].w};
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { cc[j] = c8[j]; ss[j] = s8[j]; }
+            }
             float r1[8], r2[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float u1 = (kr[n][j] * cc[j] - kr[n][8 + j] * ss[j]) * 16.f, u2 = (kr[n][8 + j] * cc[j] + kr[n][j] * ss[j]) * 16.f;
+                float u1, u2;
+                if constexpr (ROPE) {
+                    u1 = (kr[n][j] * cc[j] - kr[n][8 + j] * ss[j]) * 16.f; u2 = (kr[n][8 + j] * cc[j] + kr[n][j] * ss[j]) * 16.f;
+                } else {
+                    u1 = kr[n][j] * 16.f; u2 = kr[n][8 + j] * 16.f;
+                }
                 r1[j] = valid ? u1 : 0.f;
                 r2[j] = valid ? u2 : 0.f;
                 range_max = __builtin_fmaxf(range_max, __builtin_fmaxf(__builtin_fabsf(r1[j]), __builtin_fabsf(r2[j])));
@@ -355,19 +389,21 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ g
 
 using namespace amp;
 
-// both attention entries: `who` names the entry in the messages, `causal` picks the instantiation
-static int rope_attention_run(const char* who, bool causal, const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride,
+// the three attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false:
+// amp_mh_attention, dk = 128, cos / sin unused)
+static int rope_attention_run(const char* who, bool causal, bool rope, const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride,
                               const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale,
                               float* out_dev, void* stream) {
-    if (!q_dev || !k_dev || !v_dev || !cos_dev || !sin_dev || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
-    if (dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
+    if (!q_dev || !k_dev || !v_dev || (rope && (!cos_dev || !sin_dev)) || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
+    if (rope && dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
+    if (!rope && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
     if (B < 1 || H < 1 || T < 1) { set_error("%s: B=%d H=%d T=%d", who, B, H, T); return AMP_ERR_INVALID; }
     if (T > AT_MAX_T) { set_error("%s: T=%d is beyond %d", who, T, AT_MAX_T); return AMP_ERR_INVALID; }
     if ((long long)B * H > 65535) { set_error("%s: B*H=%lld is beyond the grid (65535)", who, (long long)B * H); return AMP_ERR_INVALID; }
     if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("%s: scale=%g", who, (double)scale); return AMP_ERR_INVALID; }
     if (batch_stride == 0) batch_stride = (long long)H * dk * T;
     if (batch_stride < (long long)H * dk * T) { set_error("%s: batch stride %lld < H*dk*T", who, batch_stride); return AMP_ERR_INVALID; }
-    if ((reinterpret_cast<uintptr_t>(cos_dev) | reinterpret_cast<uintptr_t>(sin_dev)) & 15) {
+    if (rope && ((reinterpret_cast<uintptr_t>(cos_dev) | reinterpret_cast<uintptr_t>(sin_dev)) & 15)) {
         set_error("%s: cos / sin must be 16-byte aligned", who);
         return AMP_ERR_INVALID;
     }
@@ -394,9 +430,17 @@ static int rope_attention_run(const char* who, bool causal, const float* q_dev, 
     a.c = scale * (1.0f / 256.f);
     a.range_flag = range_flag_for_current_device();
     const dim3 grid((unsigned)((T + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
-    note_kernel("rope_attention_kernel", dk, causal ? 1 : 0);
+    if (rope) note_kernel("rope_attention_kernel", dk, causal ? 1 : 0);
+    else note_kernel("rope_attention_kernel", dk, 0, 0);
     note_work((unsigned long long)grid.x * grid.y, (causal ? 0.5 : 1.0) * 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
               "rope attention%s B=%d H=%d dk=%d T=%d mask=%d", causal ? " causal" : "", B, H, dk, T, key_mask_dev ? 1 : 0);
+    if (!rope) {
+        constexpr size_t lds = attn_lds_bytes<128>();
+        AMP_HIP((ensure_dynamic_lds<rope_attention_kernel<128, false, false>>(lds)));
+        hipLaunchKernelGGL((rope_attention_kernel<128, false, false>), grid, dim3(64 * AT_NW), lds, (hipStream_t)stream, a);
+        AMP_HIP(hipGetLastError());
+        return AMP_OK;
+    }
     auto kern = dk == 64 ? (causal ? rope_attention_kernel<64, true> : rope_attention_kernel<64, false>)
                          : (causal ? rope_attention_kernel<96, true> : rope_attention_kernel<96, false>);
     hipLaunchKernelGGL(kern, grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
@@ -409,15 +453,21 @@ extern "C" {
 int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
                        const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
                        void* stream) {
-    return rope_attention_run("amp_rope_attention", false, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T, scale,
+    return rope_attention_run("amp_rope_attention", false, true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T, scale,
                               out_dev, stream);
 }
 
 int amp_rope_attention_causal(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
                               const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
                               void* stream) {
-    return rope_attention_run("amp_rope_attention_causal", true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T,
+    return rope_attention_run("amp_rope_attention_causal", true, true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T,
                               scale, out_dev, stream);
+}
+
+int amp_mh_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const unsigned char* key_mask_dev, int B,
+                     int H, int dk, int T, float scale, float* out_dev, void* stream) {
+    return rope_attention_run("amp_mh_attention", false, false, q_dev, k_dev, v_dev, batch_stride, nullptr, nullptr, key_mask_dev, B, H, dk, T, scale,
+                              out_dev, stream);
 }
 
 int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,

@@ -202,7 +202,9 @@ extern "C" {
 // 154 (additive): amp_mask_sample (maskgct.hip); amp_rope_attention at head dimension 96
 // 155 (additive): the autoregressive transformer's amp_rope_attention_causal (llama_nar.hip) and amp_kv_append, amp_attention_decode,
 // amp_pw_forward_vec and amp_ar_sample with their workspace queries (llama_ar.hip)
-int amp_version(void) { return 155; }
+// 156 (additive): FastSpeech2 / JETS inference -- amp_mh_attention (llama_nar.hip's kernel without rotation, head dimension 128) and
+// amp_fs2_durations, amp_bucketize_embed_add, amp_layer_norm_c_head (fastspeech.hip)
+int amp_version(void) { return 156; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

@@ -720,3 +720,106 @@ def ar_sample(logits, q, ids, n_ids, eos_id, suppress_eos, temperature=1.0, top_
                                             int(eos_id), 1 if suppress_eos else 0, float(temperature), int(top_k), float(top_p),
                                             float(repetition_penalty), _stream(logits)))
     return ids
+
+
+# ---- FastSpeech2 / JETS inference (csrc/fastspeech.hip; the attention is llama_nar.hip's kernel without rotation) ----------------
+def mh_attention(q, k, v, n_heads, key_mask=None, scale=None):
+    """``ScaledDotProductAttention`` inside the FFT block's ``MultiHeadAttention`` (``amp_mh_attention``): non-causal, no positional rotation.
+
+    q, k, v [B, H*dk, T] channel-first: contiguous tensors, or the three row blocks of one stacked [B, 3*H*dk, T] GEMM output (read in
+    place: no copy).  key_mask [B, T] bool / uint8, 1 = VALID (the reference's mask is 1 = padded: pass its negation), any pattern, at least
+    one valid key per item; None = all valid.  scale = 1 / temperature, default 1 / sqrt(dk).  -> [B, H*dk, T].  dk = 128.  Under the "f32"
+    precision the same formula runs as ``scaled_dot_product_attention`` in torch (not the hot path)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _f32_dev(t, name, "mh_attention")
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or k.device != q.device or v.device != q.device:
+        raise ValueError(f"mh_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    B, C, T = q.shape
+    H = int(n_heads)
+    if H < 1 or C % H:
+        raise ValueError(f"mh_attention: {C} channels do not divide into {H} heads")
+    dk = C // H
+    if dk != 128:
+        raise ValueError(f"mh_attention: head dimension {dk} is not covered (dk = 128)")
+    if B < 1 or T < 1:
+        raise ValueError(f"mh_attention: empty input {tuple(q.shape)}")
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
+            raise ValueError(f"mh_attention: key_mask must be a {(B, T)} tensor on {q.device}")
+        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
+            key_mask = (key_mask != 0).to(torch.uint8)
+        key_mask = key_mask.contiguous()
+    scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
+    with _lib.on_device(q.device):
+        if _lib.get_precision() == "f32":
+            m = None if key_mask is None else key_mask.bool()[:, None, None, :]
+            o = torch.nn.functional.scaled_dot_product_attention(*(t.reshape(B, H, dk, T).transpose(2, 3) for t in (q, k, v)), attn_mask=m,
+                                                                 scale=scale)
+            return o.transpose(2, 3).reshape(B, C, T).contiguous()
+        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
+        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            bstride = C * T
+        out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().amp_mh_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(key_mask), B, H, dk, T, scale, _ptr(out), _stream(q)))
+    return out
+
+
+def fs2_durations(log_d, d_control=1.0):
+    """log_d [B, T] -> (d_rounded [B, T] fp32 = ``clamp(round(exp(log_d) - 1) * d_control, min=0)``, cum [B, T] int32, the running sum of
+    ``int(d_rounded)`` in the layout ``expand_path`` takes, mel_len [B] int32) (``amp_fs2_durations``)"""
+    log_d = _lib.require_device_tensor(log_d, "fs2_durations input")
+    if log_d.dim() != 2 or log_d.numel() == 0:
+        raise ValueError(f"fs2_durations: expected a non-empty [B, T] input, got {tuple(log_d.shape)}")
+    B, T = log_d.shape
+    d = torch.empty_like(log_d)
+    cum = torch.empty((B, T), dtype=torch.int32, device=log_d.device)
+    mel_len = torch.empty((B,), dtype=torch.int32, device=log_d.device)
+    with _lib.on_device(log_d.device):
+        _lib.check(_lib.lib().amp_fs2_durations(_ptr(log_d), B, T, float(d_control), _ptr(d), _ptr(cum), _ptr(mel_len), _stream(log_d)))
+    return d, cum, mel_len
+
+
+def bucketize_embed_add(x, pred, control, bins, table, out=None):
+    """``x + embedding(bucketize(pred * control, bins))`` at every column, bit for bit torch's (``amp_bucketize_embed_add``): x [B, D, T]
+    channel-first, pred [B, T], bins [n_bins - 1] ascending, table [n_bins, D].  ``out`` may be ``x``.  -> (y [B, D, T], pred * control)"""
+    x = _lib.require_device_tensor(x, "bucketize_embed_add input")
+    pred = _lib.require_device_tensor(pred, "bucketize_embed_add prediction")
+    bins = _lib.require_device_tensor(bins.detach(), "bucketize_embed_add boundaries")
+    table = _lib.require_device_tensor(table.detach(), "bucketize_embed_add table")
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"bucketize_embed_add: expected a non-empty [B, D, T] input, got {tuple(x.shape)}")
+    B, D, T = x.shape
+    if tuple(pred.shape) != (B, T) or bins.dim() != 1 or table.dim() != 2 or table.shape[1] != D or table.shape[0] < bins.shape[0] + 1 or bins.shape[0] < 1:
+        raise ValueError(f"bucketize_embed_add: expected pred {(B, T)}, n boundaries and a table [>= n + 1, {D}], got {tuple(pred.shape)}, "
+                         f"{tuple(bins.shape)}, {tuple(table.shape)}")
+    if any(t.device != x.device for t in (pred, bins, table)):
+        raise ValueError(f"bucketize_embed_add: every tensor must be on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"bucketize_embed_add: out must be a contiguous float32 {tuple(x.shape)} on {x.device}")
+    scaled = torch.empty_like(pred)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_bucketize_embed_add(_ptr(pred), float(control), _ptr(bins), bins.shape[0], _ptr(table), table.shape[0], _ptr(x), B, D,
+                                                      T, _ptr(out), _ptr(scaled), _stream(x)))
+    return out, scaled
+
+
+def layer_norm_c_head(x, gamma, beta, w, b0, lens=None, eps=1e-5):
+    """``Linear(C, 1)(LN_c(x))`` as [B, T], 0 where ``t >= lens[b]`` (``amp_layer_norm_c_head``): x [B, C, T], gamma / beta / w [C], b0 a float"""
+    x = _lib.require_device_tensor(x, "layer_norm_c_head input")
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"layer_norm_c_head: expected a non-empty [B, C, T] input, got {tuple(x.shape)}")
+    B, C, T = x.shape
+    gamma, beta, w = (_lib.require_device_tensor(t.detach().reshape(-1), n) for t, n in ((gamma, "gamma"), (beta, "beta"), (w, "head weight")))
+    if any(t.numel() != C or t.device != x.device for t in (gamma, beta, w)):
+        raise ValueError(f"layer_norm_c_head: gamma, beta and w must hold {C} values on {x.device}")
+    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or lens.device != x.device):
+        raise ValueError(f"layer_norm_c_head: lens must be an int32 [{B}] tensor on {x.device}")
+    y = torch.empty((B, T), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_layer_norm_c_head(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(w), float(b0), _ptr(lens), B, C, T, float(eps), _ptr(y),
+                                                    _stream(x)))
+    return y

@@ -103,7 +103,9 @@ typedef struct amp_gen amp_gen;
  * 153 (additive): amp_rope_attention, amp_rms_norm_c_adaptive, amp_silu and amp_swiglu (the flow-matching transformer of Vevo);
  * 154 (additive): amp_mask_sample (MaskGCT's decoding step), and amp_rope_attention accepts head dimension 96 beside 64;
  * 155 (additive): amp_rope_attention_causal, amp_kv_append, amp_attention_decode (+ _workspace_bytes, _split), amp_pw_forward_vec
- * (+ _workspace_bytes) and amp_ar_sample (the autoregressive transformer of Vevo). */
+ * (+ _workspace_bytes) and amp_ar_sample (the autoregressive transformer of Vevo);
+ * 156 (additive): amp_mh_attention (head dimension 128, no rotation), amp_fs2_durations, amp_bucketize_embed_add and amp_layer_norm_c_head
+ * (FastSpeech2 / JETS inference). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -1020,6 +1022,58 @@ size_t amp_pw_forward_vec_workspace_bytes(const amp_pw* h, int B);
  * batch_stride below V, ids overlapping logits or q. */
 int amp_ar_sample(const float* logits_dev, long long batch_stride, int B, int V, const float* q_dev, long long* ids_dev, long long ids_capacity,
                   int n_ids, int eos_id, int suppress_eos, float temperature, int top_k, double top_p, float repetition_penalty, void* stream);
+
+/* ---- FastSpeech2 / JETS inference (csrc/fastspeech.hip, csrc/llama_nar.hip; models/tts/fastspeech2/fs2.py, models/tts/jets/jets.py,
+ * modules/transformer/{Models,Layers,SubLayers,Modules}.py).  Channel-first [B, C, T] fp32.  Deterministic, no atomics on data, no
+ * allocation and no synchronisation; every argument is judged on the host before anything is launched. ---- */
+
+/* ScaledDotProductAttention inside the FFT block's MultiHeadAttention, in one launch (flash-style: no [T, T] tensor):
+ *     out[b, h*dk + d, t] = sum_s softmax_s( scale * <q[b, h, :, t], k[b, h, :, s]> + mask(b, s) ) v[b, h*dk + d, s]
+ * Non-causal, NO positional rotation.  This is amp_rope_attention's kernel with its compile-time rotation switched off, and everything that
+ * entry point states holds here: q, k, v [B, H*dk, T] with rows T apart and ONE batch stride (0 = dense; the three row blocks of a stacked
+ * q | k | v GEMM output are read in place), out dense and not overlapping them; key_mask [B, T] bytes, 1 = valid, any pattern, NULL = all
+ * valid, applied to keys only; a masked key contributes exactly 0 whatever finite value its k / v columns hold; every item needs one valid
+ * key; both products split-f16 MFMA with an fp32 online softmax whatever amp_set_precision says; q, k and v are staged after an exact x16
+ * and take part in the op-level range guard (amp_range_check); T = 1 is a strided copy of v (its bits).
+ * scale: the caller's 1 / temperature = 1 / sqrt(dk) (any positive finite value).
+ * dk = 128 only (hidden 256 with 2 heads, every FastSpeech2 / JETS recipe): the K and V planes take 67 584 bytes of dynamic LDS.
+ * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk other than 128, B, H or T < 1, T > 32768, B*H > 65535, batch_stride
+ * below H*dk*T, out overlapping q / k / v. */
+int amp_mh_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const unsigned char* key_mask_dev, int B,
+                     int H, int dk, int T, float scale, float* out_dev, void* stream);
+
+/* VarianceAdaptor's durations from the (masked) log-duration prediction log_d [B, T]:
+ *     d_rounded[b, t] = max( rint( expf(log_d[b, t]) - 1 ) * d_control, 0 )        fp32 [B, T]
+ *     cum[b, t]       = sum_{s <= t} (int) d_rounded[b, s]                         int32 [B, T], the layout amp_expand_path takes
+ *     mel_len[b]      = cum[b, T - 1]                                              int32 [B]
+ * rint is round-half-even (torch.round), expf the accurate one, the multiply one fp32 multiply; the clamp keeps -0 and NaN as torch.clamp
+ * does.  (int) truncates as LengthRegulator.expand does (`max(int(expand_size), 0)`); a NaN counts 0, one token at most 2^24 frames, the sum
+ * saturates at INT_MAX.  mel_len may be 0: the caller refuses such an item.  One workgroup per item scans in a fixed order.  JETS is the same
+ * op at d_control = 1 (its .long() output is (int) d_rounded).
+ * AMP_ERR_INVALID with a message: a NULL pointer, B or T < 1, d_control not positive and finite, d_rounded aliasing log_d. */
+int amp_fs2_durations(const float* log_d_dev, int B, int T, float d_control, float* d_rounded_dev, int* cum_dev, int* mel_len_dev, void* stream);
+
+/* x + embedding(bucketize(pred * control, bins)) in one launch, as torch.bucketize(right = False) + nn.Embedding + add give it, bit for bit:
+ *     v = pred[b, t] * control (one fp32 multiply), written to pred_out[b, t]
+ *     i = the number of boundaries < v: a value equal to a boundary takes that boundary's index, below the first gives 0, above the last --
+ *         and NaN -- gives n_bounds
+ *     y[b, :, t] = x[b, :, t] + table[i, :]          (one fp32 add)
+ * at EVERY column, padded ones included (the reference adds the embedding of prediction 0 there).  pred [B, T]; bins [n_bounds] ascending;
+ * table [n_rows, D] row-major with n_rows >= n_bounds + 1 (n_bins = n_bounds + 1 in the reference); x, y [B, D, T], y may be x.  Table rows
+ * are gathered as contiguous segments and stored along T through LDS, as amp_embed_sum_c does.
+ * AMP_ERR_INVALID with a message: a NULL pointer, B, D or T < 1, n_bounds < 1, a table of fewer than n_bounds + 1 rows, a NaN control,
+ * pred_out aliasing pred; B or ceil(D / 64) beyond 65535 AMP_ERR_UNSUPPORTED. */
+int amp_bucketize_embed_add(const float* pred_dev, float control, const float* bins_dev, int n_bounds, const float* table_dev, int n_rows,
+                            const float* x_dev, int B, int D, int T, float* y_dev, float* pred_out_dev, void* stream);
+
+/* VariancePredictor's tail, layer_norm_2 -> Linear(C, 1) -> masked_fill, without writing the normalised tensor:
+ *     y[b, t] = sum_c w[c] * ( gamma[c] * (x[b, c, t] - mean_c) * rstd_c + beta[c] ) + b0,        0 (by select) where t >= lens[b]
+ * x [B, C, T], y [B, T]; lens int32 [B] or NULL (no mask).  Mean, biased variance of the centred values, their order of summation and the
+ * affine are amp_layer_norm_c's; the sum over c adds thread partials (fma, ascending channels) over the eight channel groups in a fixed order.
+ * A masked column is 0 whatever x holds there (NaN included).  Any C, T >= 1; each x element is read once for C <= 256.
+ * AMP_ERR_INVALID with a message: a NULL pointer (lens excepted), B, C or T < 1, B > 65535, a negative or NaN eps. */
+int amp_layer_norm_c_head(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* w_dev, float b0, const int* lens_dev, int B,
+                          int C, int T, float eps, float* y_dev, void* stream);
 
 #ifdef __cplusplus
 }
