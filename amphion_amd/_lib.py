@@ -215,6 +215,15 @@ _SIGNATURES = {
     "amp_ar_sample": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_float, c_int,
                               ctypes.c_double, c_float, c_void_p]),
     "amp_mh_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "amp_cross_attention": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p, c_void_p]),
+    "amp_ns2_layer_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_ns2_layer_precision": (c_int, [c_void_p]),
+    "amp_ns2_layer_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "amp_ns2_layer_forward": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_ns2_layer_destroy": (None, [c_void_p]),
+    "amp_ns2_ode_step": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "amp_fs2_durations": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "amp_bucketize_embed_add": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "amp_layer_norm_c_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

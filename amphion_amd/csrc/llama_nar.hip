@@ -3,6 +3,7 @@
 //     amp_rope_attention        non-causal multi-head self-attention with rotary position embedding and a key mask, one launch
 //     amp_rope_attention_causal the same kernel with its compile-time causal flag: the prefill of the autoregressive transformer (llama_ar.hip)
 //     amp_mh_attention          the same kernel with its compile-time rotation flag off, head dimension 128: the FFT block of FastSpeech2 / JETS
+//     amp_cross_attention       the same, head dimension 64, with query and key extents and batch strides apart: every attention of NaturalSpeech2
 //     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
 //     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
 // Everything is channel-first [B, C, T] fp32.  Deterministic: no atomics on data (the attention kernel ORs the op-level range flag).
@@ -40,12 +41,13 @@ struct AttnArgs {
     const float* q;
     const float* k;
     const float* v;
-    long long bstride;             // elements between items of q / k / v
-    const float* cs;               // [T, DK / 2]
+    long long qbstride;            // elements between items of q
+    long long kvbstride;           // elements between items of k / v (self-attention: both are the stride of the stacked q | k | v tensor)
+    const float* cs;               // [T, DK / 2]: rotation only, where Tq == Tk
     const float* sn;
-    const unsigned char* mask;     // [B, T] or nullptr
-    float* out;                    // [B, H * DK, T]
-    int H, T;
+    const unsigned char* mask;     // [B, Tk] or nullptr
+    float* out;                    // [B, H * DK, Tq]
+    int H, Tq, Tk;                 // queries (rows of q and out are Tq apart) and keys (rows of k and v are Tk apart); equal except for amp_cross_attention
     float c;                       // scale / 256: un-does the two x16 of the staged operands (a power of two at DK = 64 only: one rounding at 96)
     unsigned* range_flag;
 };
@@ -80,24 +82,24 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
     const int b = blockIdx.y / a.H, h = blockIdx.y - b * a.H;
-    const int T = a.T;
-    const size_t head = (size_t)b * (size_t)a.bstride + (size_t)h * AT_DK * T;
-    const float* __restrict__ qb = a.q + head;
-    const float* __restrict__ kb = a.k + head;
-    const float* __restrict__ vb = a.v + head;
+    const int Tq = a.Tq, T = a.Tk;
+    const size_t khead = (size_t)b * (size_t)a.kvbstride + (size_t)h * AT_DK * T;
+    const float* __restrict__ qb = a.q + (size_t)b * (size_t)a.qbstride + (size_t)h * AT_DK * Tq;
+    const float* __restrict__ kb = a.k + khead;
+    const float* __restrict__ vb = a.v + khead;
     const unsigned char* __restrict__ mk = a.mask ? a.mask + (size_t)b * T : nullptr;
     float range_max = 0.f;
 
     // ---- Q' fragments: lane (l31, hi) holds channels 16 s + 8 hi + j of query l31; channel i < HALF and its partner i + HALF are s and s + NP
     const int tq = blockIdx.x * AT_TQ + 32 * w + l31;
-    const int tqc = tq < T ? tq : T - 1;
+    const int tqc = tq < Tq ? tq : Tq - 1;
     Frag qh[NF], ql[NF];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int i = 16 * p + 8 * hi + j;
-            const float x1 = qb[(size_t)i * T + tqc], x2 = qb[(size_t)(i + HALF) * T + tqc];
+            const float x1 = qb[(size_t)i * Tq + tqc], x2 = qb[(size_t)(i + HALF) * Tq + tqc];
             float r1, r2;
             if constexpr (ROPE) {
                 const float c = a.cs[(size_t)tqc * HALF + i], s = a.sn[(size_t)tqc * HALF + i];
@@ -292,12 +294,12 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
 
     const float lt = l + __shfl_xor(l, 32);
     const float inv = (1.0f / lt) * (1.0f / 16384.f);      // x16 of V, x1024 of P
-    if (tq < T) {
-        float* ob = a.out + ((size_t)blockIdx.y * AT_DK) * T + tq;
+    if (tq < Tq) {
+        float* ob = a.out + ((size_t)blockIdx.y * AT_DK) * Tq + tq;
 #pragma unroll
         for (int db = 0; db < ND; ++db)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) ob[(size_t)acc_row(r, hi, 32 * db) * T] = O[db][0][r] * inv;
+            for (int r = 0; r < 16; ++r) ob[(size_t)acc_row(r, hi, 32 * db) * Tq] = O[db][0][r] * inv;
     }
     raise_range(a.range_flag, range_max, lane);
 }
@@ -385,53 +387,87 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const float* __restrict__ g
     }
 }
 
+// ---- amp_cross_attention at Tk = 1: out[b, c, tq] = v[b, c, 0] for every query (the softmax over one key is exactly 1) -------------------
+__global__ __launch_bounds__(256) void attn_one_key_kernel(const float* __restrict__ v, long long vbs, float* __restrict__ out, int C, int Tq) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < Tq) out[((size_t)blockIdx.z * C + blockIdx.y) * Tq + t] = v[(size_t)blockIdx.z * (size_t)vbs + blockIdx.y];
+}
+
 }  // namespace amp
 
 using namespace amp;
 
-// the three attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false:
-// amp_mh_attention, dk = 128, cos / sin unused)
-static int rope_attention_run(const char* who, bool causal, bool rope, const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride,
-                              const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale,
-                              float* out_dev, void* stream) {
+// the four attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false: amp_mh_attention at
+// dk = 128 and, with `cross`, amp_cross_attention at dk = 64; cos / sin unused).  Tq != Tk and q_stride != kv_stride come from amp_cross_attention only.
+static int rope_attention_run(const char* who, bool causal, bool rope, bool cross, const float* q_dev, long long q_stride, const float* k_dev, const float* v_dev,
+                              long long kv_stride, const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk,
+                              int Tq, int T, float scale, float* out_dev, void* stream) {
     if (!q_dev || !k_dev || !v_dev || (rope && (!cos_dev || !sin_dev)) || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
     if (rope && dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
-    if (!rope && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
-    if (B < 1 || H < 1 || T < 1) { set_error("%s: B=%d H=%d T=%d", who, B, H, T); return AMP_ERR_INVALID; }
-    if (T > AT_MAX_T) { set_error("%s: T=%d is beyond %d", who, T, AT_MAX_T); return AMP_ERR_INVALID; }
+    if (!rope && !cross && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
+    if (cross && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
+    if (cross) {
+        if (B < 1 || H < 1 || Tq < 1 || T < 1) { set_error("%s: B=%d H=%d Tq=%d Tk=%d", who, B, H, Tq, T); return AMP_ERR_INVALID; }
+        if (Tq > AT_MAX_T || T > AT_MAX_T) { set_error("%s: Tq=%d / Tk=%d is beyond %d", who, Tq, T, AT_MAX_T); return AMP_ERR_INVALID; }
+    } else {
+        if (B < 1 || H < 1 || T < 1) { set_error("%s: B=%d H=%d T=%d", who, B, H, T); return AMP_ERR_INVALID; }
+        if (T > AT_MAX_T) { set_error("%s: T=%d is beyond %d", who, T, AT_MAX_T); return AMP_ERR_INVALID; }
+    }
     if ((long long)B * H > 65535) { set_error("%s: B*H=%lld is beyond the grid (65535)", who, (long long)B * H); return AMP_ERR_INVALID; }
     if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("%s: scale=%g", who, (double)scale); return AMP_ERR_INVALID; }
-    if (batch_stride == 0) batch_stride = (long long)H * dk * T;
-    if (batch_stride < (long long)H * dk * T) { set_error("%s: batch stride %lld < H*dk*T", who, batch_stride); return AMP_ERR_INVALID; }
+    if (kv_stride == 0) kv_stride = (long long)H * dk * T;
+    if (q_stride == 0) q_stride = (long long)H * dk * Tq;
+    if (kv_stride < (long long)H * dk * T) { set_error("%s: batch stride %lld < H*dk*T", who, kv_stride); return AMP_ERR_INVALID; }
+    if (q_stride < (long long)H * dk * Tq) { set_error("%s: q batch stride %lld < H*dk*Tq", who, q_stride); return AMP_ERR_INVALID; }
     if (rope && ((reinterpret_cast<uintptr_t>(cos_dev) | reinterpret_cast<uintptr_t>(sin_dev)) & 15)) {
         set_error("%s: cos / sin must be 16-byte aligned", who);
         return AMP_ERR_INVALID;
     }
-    const size_t span = (size_t)(B - 1) * (size_t)batch_stride + (size_t)H * dk * T;
+    const size_t qspan = (size_t)(B - 1) * (size_t)q_stride + (size_t)H * dk * Tq;
+    const size_t kspan = (size_t)(B - 1) * (size_t)kv_stride + (size_t)H * dk * T;
     const float* olo = out_dev;
-    const float* ohi = out_dev + (size_t)B * H * dk * T;
-    for (const float* p : {q_dev, k_dev, v_dev})
-        if (p < ohi && olo < p + span) { set_error("%s: out must not overlap q / k / v", who); return AMP_ERR_INVALID; }
-    if (T == 1) {
+    const float* ohi = out_dev + (size_t)B * H * dk * Tq;
+    if ((q_dev < ohi && olo < q_dev + qspan) || (k_dev < ohi && olo < k_dev + kspan) || (v_dev < ohi && olo < v_dev + kspan)) {
+        set_error("%s: out must not overlap q / k / v", who);
+        return AMP_ERR_INVALID;
+    }
+    if (T == 1 && Tq == 1) {
         // One key (query 0 sees key 0 under the causal rule too): the softmax over it is exactly 1 whatever q and k hold (the item's one key
         // is valid, see the header), so the attention is the identity on v and there is no product to form.  A strided copy returns v's bits, as the fp32 reference does (1.0f * v),
         // where the split-f16 operand of the kernel would return 22 of its 24 mantissa bits.
-        AMP_HIP(hipMemcpy2DAsync(out_dev, (size_t)H * dk * sizeof(float), v_dev, (size_t)batch_stride * sizeof(float),
+        AMP_HIP(hipMemcpy2DAsync(out_dev, (size_t)H * dk * sizeof(float), v_dev, (size_t)kv_stride * sizeof(float),
                                  (size_t)H * dk * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return AMP_OK;
+    }
+    if (T == 1) {
+        // amp_cross_attention with one key and several queries: the same identity, v's column written to every query column
+        const dim3 grid((unsigned)((Tq + 255) / 256), (unsigned)(H * dk), (unsigned)B);
+        if (grid.y > 65535 || grid.z > 65535) { set_error("%s: H*dk=%d or B=%d is beyond the grid (65535)", who, H * dk, B); return AMP_ERR_INVALID; }
+        note_kernel("attn_one_key_kernel");
+        note_work((unsigned long long)grid.x * grid.y * grid.z, 0.0, 4.0 * (double)B * H * dk * Tq / 1e6, "cross attention Tk=1 B=%d H=%d dk=%d Tq=%d", B, H, dk, Tq);
+        hipLaunchKernelGGL(attn_one_key_kernel, grid, dim3(256), 0, (hipStream_t)stream, v_dev, kv_stride, out_dev, H * dk, Tq);
+        AMP_HIP(hipGetLastError());
         return AMP_OK;
     }
     AttnArgs a{};
     a.q = q_dev; a.k = k_dev; a.v = v_dev;
-    a.bstride = batch_stride;
+    a.qbstride = q_stride; a.kvbstride = kv_stride;
     a.cs = cos_dev; a.sn = sin_dev;
     a.mask = key_mask_dev;
     a.out = out_dev;
-    a.H = H; a.T = T;
+    a.H = H; a.Tq = Tq; a.Tk = T;
     a.c = scale * (1.0f / 256.f);
     a.range_flag = range_flag_for_current_device();
-    const dim3 grid((unsigned)((T + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
+    const dim3 grid((unsigned)((Tq + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
     if (rope) note_kernel("rope_attention_kernel", dk, causal ? 1 : 0);
     else note_kernel("rope_attention_kernel", dk, 0, 0);
+    if (cross) {
+        note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)Tq * T / 1e9, 8.0 * (double)B * H * dk * ((double)Tq + T) / 1e6,
+                  "cross attention B=%d H=%d dk=%d Tq=%d Tk=%d mask=%d", B, H, dk, Tq, T, key_mask_dev ? 1 : 0);
+        hipLaunchKernelGGL((rope_attention_kernel<64, false, false>), grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+        AMP_HIP(hipGetLastError());
+        return AMP_OK;
+    }
     note_work((unsigned long long)grid.x * grid.y, (causal ? 0.5 : 1.0) * 4.0 * 3.0 * (double)B * H * dk * (double)T * T / 1e9, 16.0 * (double)B * H * dk * T / 1e6,
               "rope attention%s B=%d H=%d dk=%d T=%d mask=%d", causal ? " causal" : "", B, H, dk, T, key_mask_dev ? 1 : 0);
     if (!rope) {
@@ -453,21 +489,27 @@ extern "C" {
 int amp_rope_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
                        const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
                        void* stream) {
-    return rope_attention_run("amp_rope_attention", false, true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T, scale,
-                              out_dev, stream);
+    return rope_attention_run("amp_rope_attention", false, true, false, q_dev, batch_stride, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk,
+                              T, T, scale, out_dev, stream);
 }
 
 int amp_rope_attention_causal(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const float* cos_dev,
                               const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk, int T, float scale, float* out_dev,
                               void* stream) {
-    return rope_attention_run("amp_rope_attention_causal", true, true, q_dev, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B, H, dk, T,
-                              scale, out_dev, stream);
+    return rope_attention_run("amp_rope_attention_causal", true, true, false, q_dev, batch_stride, k_dev, v_dev, batch_stride, cos_dev, sin_dev, key_mask_dev, B,
+                              H, dk, T, T, scale, out_dev, stream);
 }
 
 int amp_mh_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const unsigned char* key_mask_dev, int B,
                      int H, int dk, int T, float scale, float* out_dev, void* stream) {
-    return rope_attention_run("amp_mh_attention", false, false, q_dev, k_dev, v_dev, batch_stride, nullptr, nullptr, key_mask_dev, B, H, dk, T, scale,
-                              out_dev, stream);
+    return rope_attention_run("amp_mh_attention", false, false, false, q_dev, batch_stride, k_dev, v_dev, batch_stride, nullptr, nullptr, key_mask_dev, B, H, dk, T,
+                              T, scale, out_dev, stream);
+}
+
+int amp_cross_attention(const float* q_dev, long long q_batch_stride, const float* k_dev, const float* v_dev, long long kv_batch_stride,
+                        const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream) {
+    return rope_attention_run("amp_cross_attention", false, false, true, q_dev, q_batch_stride, k_dev, v_dev, kv_batch_stride, nullptr, nullptr, key_mask_dev, B,
+                              H, dk, Tq, Tk, scale, out_dev, stream);
 }
 
 int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,

@@ -5,6 +5,8 @@
 //     AMP_PW_BIAS        y = Wx + b
 //     AMP_PW_BIAS_GELU   y = gelu_erf(Wx + b)                 (nn.GELU(), exact erf form)
 //     AMP_PW_SCALE_RES   y = res + gamma (.) (Wx + b)         (layer scale + residual; y may alias res)
+//     PW_EPI_RES_SKIP    rows [0, H): y = (res + v) / sqrt(2); rows [H, 2H): skip_out = skip_in + v, v = Wx + b   (internal, Cout = 2H: out_proj of
+//                        NaturalSpeech2's WaveNet layer, ns2_layer_f16x3.hip; y, res, skip_in, skip_out are [B, H, T]; y may alias res, skip_out skip_in)
 //
 // Arithmetic: the f16x3 scheme (f16x3_device.h; operand layouts and fragment loads: wholek_f16x3.h) -- weights pre-split on the host after a
 // per-matrix 2^s, activations x16 and split while staged, the scale undone in the epilogue, the range flag raised by the staging.
@@ -31,6 +33,7 @@ namespace amp {
 constexpr int PW_KS = 4;            // MFMA k-extents (16 channels each) per K step
 constexpr int PW_KC = 16 * PW_KS;   // channels per K step
 constexpr int PW_MROWS = 128;       // packed rows are padded to this (the larger tile's height)
+constexpr int PW_EPI_RES_SKIP = 3;  // beyond amp_pw_epilogue: reached through pw_run_res_skip only
 
 struct PwArgs {
     const float* x;       // [B, Cin, T] with batch stride xbs
@@ -46,6 +49,8 @@ struct PwArgs {
     int tiles_per_item;   // ceil(T / TN)
     float inv_scale;      // 1 / (16 * 2^s)
     unsigned* range_flag;
+    const float* skip_in;   // PW_EPI_RES_SKIP: [B, Cout / 2, T] running skip sum or nullptr; may alias skip_out
+    float* skip_out;        //                  [B, Cout / 2, T]
 };
 
 template <int EPI, int MI, int NI>
@@ -162,6 +167,21 @@ __global__ __launch_bounds__(256, 2) void pw_f16x3_kernel(const PwArgs a) {
             const int m = acc_row(r, hi, (mb0 + i) * 32);
             if (m >= a.Cout) continue;
             const float bv = a.bias[m];
+            if (EPI == PW_EPI_RES_SKIP) {
+                const int Hh = a.Cout >> 1;
+                const bool sk = m >= Hh;
+                const size_t hrow = ((size_t)item * Hh + (sk ? m - Hh : m)) * T;
+                const float sqrt2 = 1.41421356237309504880f;
+#pragma unroll
+                for (int t = 0; t < NI; ++t) {
+                    const int q = q0 + wn * (32 * NI) + 32 * t + l31;
+                    if (q >= T) continue;
+                    const float v = acc[i][t][r] * a.inv_scale + bv;
+                    if (sk) a.skip_out[hrow + q] = a.skip_in ? a.skip_in[hrow + q] + v : v;
+                    else a.y[hrow + q] = (a.res[hrow + q] + v) / sqrt2;
+                }
+                continue;
+            }
             const float gv = EPI == AMP_PW_SCALE_RES ? a.gamma[m] : 0.f;
             const size_t row = ybase + (size_t)m * T;
 #pragma unroll
@@ -186,7 +206,7 @@ static hipError_t pw_launch_one(const PwArgs& a, int B, hipStream_t stream) {
     note_kernel("pw_f16x3_kernel", EPI, MI, NI);
     if (manifest_on()) {
         const double gf = 2.0 * a.Cout * (double)a.Cin * a.T * B / 1e9;
-        const double mb = 4.0 * B * ((double)a.Cin * a.T + (double)a.Cout * a.T * (EPI == AMP_PW_SCALE_RES ? 2 : 1)) / 1e6;
+        const double mb = 4.0 * B * ((double)a.Cin * a.T + (double)a.Cout * a.T * (EPI == AMP_PW_SCALE_RES || EPI == PW_EPI_RES_SKIP ? 2 : 1)) / 1e6;
         note_work((unsigned long long)grid.x * grid.y, gf, mb, "pw %d->%d epi=%d T=%d B=%d grid=%ux%u", a.Cin, a.Cout, EPI, a.T, B, grid.x, grid.y);
     }
     hipLaunchKernelGGL((pw_f16x3_kernel<EPI, MI, NI>), grid, dim3(256), lds, stream, a);
@@ -203,6 +223,31 @@ static hipError_t pw_launch(PwArgs a, int B, hipStream_t stream) {
     }
     a.tiles_per_item = (a.T + 63) / 64;
     return pw_launch_one<EPI, 1, 1>(a, B, stream);
+}
+
+// out_proj of NaturalSpeech2's WaveNet layer on an f16x3 handle with cout = 2 cin: the caller (ns2_layer_f16x3.hip) has judged the arguments
+int pw_run_res_skip(const amp_pw* p, const float* z_dev, int B, int T, const float* x_dev, const float* skip_in_dev, float* x_out_dev,
+                    float* skip_out_dev, hipStream_t stream) {
+    if (!p || p->precision != PREC_F16X3 || p->cout != 2 * p->cin) { set_error("pw_run_res_skip: not an f16x3 H -> 2H handle"); return AMP_ERR_INVALID; }
+    PwArgs a{};
+    a.x = z_dev;
+    a.xbs = (long long)p->cin * T;
+    a.wp = p->wp_dev;
+    a.bias = p->bias_dev;
+    a.res = x_dev;
+    a.y = x_out_dev;
+    a.skip_in = skip_in_dev;
+    a.skip_out = skip_out_dev;
+    a.Cin = p->cin;
+    a.Cout = p->cout;
+    a.T = T;
+    a.nsteps = p->nsteps;
+    a.nc16 = p->nsteps * PW_KS;
+    a.inv_scale = p->inv_scale;
+    a.range_flag = range_flag_for_current_device();
+    const hipError_t e = pw_launch<PW_EPI_RES_SKIP>(a, B, stream);
+    if (e != hipSuccess) { set_error("pw_run_res_skip: %s", hipGetErrorString(e)); return AMP_ERR_HIP; }
+    return AMP_OK;
 }
 
 // exact-fp32 mode: the k = 1 conv (conv_mfma.hip) writes Wx + b, this applies the rest of the epilogue in place

@@ -204,7 +204,9 @@ extern "C" {
 // amp_pw_forward_vec and amp_ar_sample with their workspace queries (llama_ar.hip)
 // 156 (additive): FastSpeech2 / JETS inference -- amp_mh_attention (llama_nar.hip's kernel without rotation, head dimension 128) and
 // amp_fs2_durations, amp_bucketize_embed_add, amp_layer_norm_c_head (fastspeech.hip)
-int amp_version(void) { return 156; }
+// 157 (additive): NaturalSpeech2 inference -- amp_cross_attention (llama_nar.hip's kernel without rotation at head dimension 64, separate query and
+// key extents), amp_ns2_layer_* (ns2_layer_f16x3.hip) and amp_ns2_ode_step (ns2.hip)
+int amp_version(void) { return 157; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from amphion_amd import _lib
-from amphion_amd._handle import HandleCache, host_f32
+from amphion_amd._handle import HandleCache, host_f32, param_sig
 from amphion_amd._lib import ptr as _ptr
 from amphion_amd.models.vocoders.gan.generator._engine import ConvParams
 
@@ -823,3 +823,139 @@ def layer_norm_c_head(x, gamma, beta, w, b0, lens=None, eps=1e-5):
         _lib.check(_lib.lib().amp_layer_norm_c_head(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(w), float(b0), _ptr(lens), B, C, T, float(eps), _ptr(y),
                                                     _stream(x)))
     return y
+
+
+# ---- NaturalSpeech2 inference (csrc/llama_nar.hip: amp_cross_attention; csrc/ns2_layer_f16x3.hip; csrc/ns2.hip) ----------------
+def cross_attention(q, k, v, n_heads, key_mask=None, scale=None):
+    """Non-causal multi-head attention without rotation at head dimension 64, query and key lengths apart (``amp_cross_attention``).
+
+    q [B, H*dk, Tq]; k, v [B, H*dk, Tk] of one shape and ONE batch stride: contiguous tensors, or row blocks of stacked GEMM outputs read in
+    place (k | v of one tensor; for self-attention q | k | v of one tensor).  key_mask [B, Tk] bool / uint8, 1 = VALID, any pattern, at least
+    one valid key per item; None = all valid.  scale defaults to 1 / sqrt(dk).  -> [B, H*dk, Tq].  Under the "f32" precision the same formula
+    runs as ``scaled_dot_product_attention`` in torch (not the hot path)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _f32_dev(t, name, "cross_attention")
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[:2] != k.shape[:2] or k.device != q.device or v.device != q.device:
+        raise ValueError(f"cross_attention: q must be [B, H*dk, Tq] and k, v [B, H*dk, Tk] on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    B, C, Tq = q.shape
+    Tk = k.shape[2]
+    H = int(n_heads)
+    if H < 1 or C % H:
+        raise ValueError(f"cross_attention: {C} channels do not divide into {H} heads")
+    dk = C // H
+    if dk != 64:
+        raise ValueError(f"cross_attention: head dimension {dk} is not covered (dk = 64)")
+    if B < 1 or Tq < 1 or Tk < 1:
+        raise ValueError(f"cross_attention: empty input {tuple(q.shape)}, {tuple(k.shape)}")
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, Tk) or key_mask.device != q.device:
+            raise ValueError(f"cross_attention: key_mask must be a {(B, Tk)} tensor on {q.device}")
+        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
+            key_mask = (key_mask != 0).to(torch.uint8)
+        key_mask = key_mask.contiguous()
+    scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
+    with _lib.on_device(q.device):
+        if _lib.get_precision() == "f32":
+            m = None if key_mask is None else key_mask.bool()[:, None, None, :]
+            qq = q.reshape(B, H, dk, Tq).transpose(2, 3)
+            kk, vv = (t.reshape(B, H, dk, Tk).transpose(2, 3) for t in (k, v))
+            o = torch.nn.functional.scaled_dot_product_attention(qq, kk, vv, attn_mask=m, scale=scale)
+            return o.transpose(2, 3).reshape(B, C, Tq).contiguous()
+        qbs = q.stride(0) if B > 1 else max(q.stride(0), C * Tq)
+        if not _rows_view(q, C, Tq, qbs) or qbs < C * Tq:
+            q, qbs = q.contiguous(), C * Tq
+        kvbs = k.stride(0) if B > 1 else max(k.stride(0), C * Tk)
+        if not (_rows_view(k, C, Tk, kvbs) and _rows_view(v, C, Tk, kvbs)) or kvbs < C * Tk:
+            k, v, kvbs = k.contiguous(), v.contiguous(), C * Tk
+        out = torch.empty((B, C, Tq), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().amp_cross_attention(_ptr(q), int(qbs), _ptr(k), _ptr(v), int(kvbs), _ptr(key_mask), B, H, dk, Tq, Tk, scale, _ptr(out),
+                                                  _stream(q)))
+    return out
+
+
+class Ns2Layer:
+    """One residual layer of NaturalSpeech2's WaveNet (``amp_ns2_layer_*``; wavenet.py:96-127 with ``x_mask = None``) over the parameters of
+    the reference's ``ResidualBlock``: ``dilated_conv`` (weight [2H, H, 3], bias) and ``out_proj`` (weight [2H, H, 1], bias).  The packed
+    device copy is rebuilt when a parameter, the device or the precision changes."""
+
+    def __init__(self, hidden, dilation):
+        self.hidden, self.dilation = int(hidden), int(dilation)
+        self._cache = HandleCache("amp_ns2_layer_destroy")
+
+    def _build(self, conv_w, conv_b, out_w, out_b, device):
+        H = self.hidden
+        cw, cb, ow, ob = host_f32(conv_w), host_f32(conv_b), host_f32(out_w), host_f32(out_b)
+        if tuple(cw.shape) != (2 * H, H, 3) or ow.numel() != 2 * H * H or (cb is not None and cb.numel() != 2 * H) or (ob is not None and ob.numel() != 2 * H):
+            raise ValueError(f"Ns2Layer: expected dilated_conv.weight {(2 * H, H, 3)} and out_proj.weight {(2 * H, H, 1)}, got {tuple(cw.shape)} and "
+                             f"{tuple(ow.shape)}")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().amp_ns2_layer_create(H, self.dilation, _ptr(cw), _ptr(cb), _ptr(ow), _ptr(ob), ctypes.byref(h)))
+        return h
+
+    def handle(self, conv_w, conv_b, out_w, out_b, device):
+        """the ``amp_ns2_layer`` handle for these parameters on ``device`` under the current precision (built on first use, rebuilt when one of
+        them changes).  A caller that runs the layer many times on buffers of its own (``WaveNet.step``) takes the handle once and calls
+        ``amp_ns2_layer_forward`` itself; ``__call__`` is the checked form."""
+        sig = param_sig((conv_w, conv_b, out_w, out_b), device, _lib.get_precision())
+        c = self._cache
+        return c.handle if sig == c.sig else c.build(sig, self._build, conv_w, conv_b, out_w, out_b, device)
+
+    def __call__(self, x, dconst, cterm, conv_w, conv_b, out_w, out_b, film=None, skip=None, x_out=None):
+        """x [B, H, T]; dconst [H] or [B, H] (rows may be a slice of a wider tensor); cterm [B, 2H, T], contiguous or a row block of a wider
+        [B, n, T] tensor; film [B, 4H, T] (gain | bias) or None; skip [B, H, T]: the running skip sum, updated IN PLACE, or None in the first
+        layer (a new tensor is returned).  x_out: where the layer's output goes (may be ``x``), default a new tensor.  -> (x_out, skip)"""
+        x = _lib.require_device_tensor(x, "ns2 layer input")
+        if x.dim() != 3 or x.shape[1] != self.hidden or x.numel() == 0:
+            raise ValueError(f"Ns2Layer: expected a non-empty [B, {self.hidden}, T] input, got {tuple(x.shape)}")
+        B, H, T = x.shape
+        dev = x.device
+        _f32_dev(dconst, "dconst", "Ns2Layer")
+        _f32_dev(cterm, "cterm", "Ns2Layer")
+        if dconst.dim() == 1:
+            dconst = dconst[None]
+        if dconst.dim() != 2 or dconst.shape[1] != H or dconst.shape[0] not in (1, B) or dconst.device != dev:
+            raise ValueError(f"Ns2Layer: dconst must be [{H}] or [{B}, {H}] on {dev}, got {tuple(dconst.shape)}")
+        if dconst.stride(1) != 1 or (dconst.shape[0] > 1 and dconst.stride(0) < H):
+            dconst = dconst.contiguous()
+        dbs = int(dconst.stride(0)) if dconst.shape[0] > 1 else 0
+        if tuple(cterm.shape) != (B, 2 * H, T) or cterm.device != dev:
+            raise ValueError(f"Ns2Layer: cterm must be {(B, 2 * H, T)} on {dev}, got {tuple(cterm.shape)}")
+        cbs = cterm.stride(0) if B > 1 else max(cterm.stride(0), 2 * H * T)
+        if not _rows_view(cterm, 2 * H, T, cbs) or cbs < 2 * H * T:
+            cterm, cbs = cterm.contiguous(), 2 * H * T
+        if film is not None:
+            film = _lib.require_device_tensor(film, "ns2 layer FiLM")
+            if tuple(film.shape) != (B, 4 * H, T) or film.device != dev:
+                raise ValueError(f"Ns2Layer: film must be {(B, 4 * H, T)} on {dev}, got {tuple(film.shape)}")
+        for t, name in ((skip, "skip"), (x_out, "x_out")):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.shape != x.shape or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"Ns2Layer: {name} must be a contiguous float32 {tuple(x.shape)} on {dev}")
+        skip_out = torch.empty_like(x) if skip is None else skip
+        x_out = torch.empty_like(x) if x_out is None else x_out
+        h = self.handle(conv_w, conv_b, out_w, out_b, dev)
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            nbytes = L.amp_ns2_layer_workspace_bytes(h, B, T)
+            ws = _workspace(dev, nbytes)
+            _lib.check(L.amp_ns2_layer_forward(h, _ptr(x), _ptr(dconst), dbs, _ptr(cterm), int(cbs), _ptr(film), _ptr(skip), B, T, _ptr(x_out),
+                                               _ptr(skip_out), _ptr(ws), nbytes, _stream(x)))
+        return x_out, skip_out
+
+
+def ns2_ode_step(x_eval, x0_pred, x_base, mean_scale, variance, h_beta, inv_sigma2, midpoint_half=False, out=None):
+    """The element-wise tail of ``Diffusion.cal_dxt`` and the solver's update in one launch (``amp_ns2_ode_step``):
+    ``x_base - dxt(x_eval, x0_pred)``, or ``0.5 * ((x_base - dxt) + x_base)`` with ``midpoint_half`` (the midpoint solver's ``x_mid``).
+    The four scalars are Python floats holding fp32 values.  ``out`` may be any of the inputs; default a new tensor."""
+    ts = [_lib.require_device_tensor(t, n) for t, n in ((x_eval, "ns2_ode_step x_eval"), (x0_pred, "ns2_ode_step x0_pred"), (x_base, "ns2_ode_step x_base"))]
+    if ts[0].numel() == 0 or ts[1].shape != ts[0].shape or ts[2].shape != ts[0].shape or ts[1].device != ts[0].device or ts[2].device != ts[0].device:
+        raise ValueError(f"ns2_ode_step: three non-empty tensors of one shape on one device, got {[tuple(t.shape) for t in ts]}")
+    if out is None:
+        out = torch.empty_like(ts[0])
+    elif out.shape != ts[0].shape or out.device != ts[0].device or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"ns2_ode_step: out must be a contiguous float32 {tuple(ts[0].shape)} on {ts[0].device}")
+    with _lib.on_device(out.device):
+        _lib.check(_lib.lib().amp_ns2_ode_step(_ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), ts[0].numel(), float(mean_scale), float(variance), float(h_beta),
+                                               float(inv_sigma2), 1 if midpoint_half else 0, _ptr(out), _stream(out)))
+    return out

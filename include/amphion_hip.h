@@ -105,7 +105,9 @@ typedef struct amp_gen amp_gen;
  * 155 (additive): amp_rope_attention_causal, amp_kv_append, amp_attention_decode (+ _workspace_bytes, _split), amp_pw_forward_vec
  * (+ _workspace_bytes) and amp_ar_sample (the autoregressive transformer of Vevo);
  * 156 (additive): amp_mh_attention (head dimension 128, no rotation), amp_fs2_durations, amp_bucketize_embed_add and amp_layer_norm_c_head
- * (FastSpeech2 / JETS inference). */
+ * (FastSpeech2 / JETS inference);
+ * 157 (additive): amp_cross_attention (head dimension 64, no rotation, separate query and key lengths), amp_ns2_layer_* and amp_ns2_ode_step
+ * (NaturalSpeech2 inference). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -1074,6 +1076,67 @@ int amp_bucketize_embed_add(const float* pred_dev, float control, const float* b
  * AMP_ERR_INVALID with a message: a NULL pointer (lens excepted), B, C or T < 1, B > 65535, a negative or NaN eps. */
 int amp_layer_norm_c_head(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* w_dev, float b0, const int* lens_dev, int B,
                           int C, int T, float eps, float* y_dev, void* stream);
+
+/* ---- NaturalSpeech2 inference (csrc/llama_nar.hip, csrc/ns2_layer_f16x3.hip, csrc/ns2.hip; models/tts/naturalspeech2/{ns2,prior_encoder,
+ * diffusion,wavenet}.py, modules/naturalpseech2/transformers.py).  Channel-first [B, C, T] fp32.  Deterministic, no atomics on data, no
+ * allocation and no synchronisation; every argument is judged on the host before anything is launched. ---- */
+
+/* Non-causal multi-head attention WITHOUT rotation at head dimension 64 with separate query and key lengths, in one launch:
+ *     out[b, h*dk + d, tq] = sum_s softmax_s( scale * <q[b, h, :, tq], k[b, h, :, s]> + mask(b, s) ) v[b, h*dk + d, s]
+ * q [B, H*dk, Tq] with rows Tq apart and its own batch stride q_batch_stride (0 = dense, H*dk*Tq); k and v [B, H*dk, Tk] with rows Tk apart
+ * and ONE batch stride kv_batch_stride (0 = dense): the two row blocks of a stacked k | v GEMM output are read in place.  Self-attention is
+ * the case Tq = Tk with all three slices of one stacked q | k | v tensor (both strides 3*H*dk*T).  key_mask [B, Tk] bytes, 1 = valid, any
+ * pattern, or NULL; out [B, H*dk, Tq] dense, not overlapping q / k / v.
+ * This is amp_mh_attention's kernel (the rotation compiled out) at dk = 64, and everything that entry point states holds with T read as Tk
+ * for keys and Tq for queries: the mask applies to keys only and every query column is computed; a masked key contributes exactly 0
+ * whatever finite value its k / v columns hold; every item needs one valid key; both products split-f16 MFMA with an fp32 online softmax
+ * whatever amp_set_precision says (the exact-fp32 route of the drop-in modules is torch's scaled_dot_product_attention); q, k and v are
+ * staged after an exact x16 and take part in the op-level range guard (amp_range_check; masked keys do not).
+ * Tk = 1 is not a launch of that kernel: the softmax over one key is exactly 1, so v's column is copied (its bits) to every query column.
+ * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk other than 64, B, H, Tq or Tk < 1, Tq or Tk > 32768, B*H > 65535,
+ * q_batch_stride below H*dk*Tq, kv_batch_stride below H*dk*Tk, a non-positive or non-finite scale, out overlapping q / k / v. */
+int amp_cross_attention(const float* q_dev, long long q_batch_stride, const float* k_dev, const float* v_dev, long long kv_batch_stride,
+                        const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream);
+
+/* One residual layer of the WaveNet (wavenet.py:96-127, ResidualBlock.forward with x_mask = None) at hidden size H:
+ *     y     = x + dconst[b, :]                          diffusion_proj(step embedding): [H] per item, dconst_batch_stride apart (0 = one row)
+ *     a     = dilated_conv_k3(y) + bias + cterm         the conv pads y, NOT x: a tap outside [0, T) contributes 0; cterm [B, 2H, T] with rows
+ *                                                       T apart and items cterm_batch_stride apart (0 = dense): cond_proj's output with its bias,
+ *                                                       e.g. one layer's row block of a GEMM stacked over all layers
+ *     a     = a * gain + fbias                          film_dev [B, 4H, T] dense, gain = rows [0, 2H), fbias = rows [2H, 4H); NULL = no FiLM
+ *     z     = sigmoid(a[:H]) * tanh(a[H:])
+ *     r     = out_proj(z)                               H -> 2H
+ *     x_out = (x + r[:H]) / sqrt(2),  skip_out = skip_in + r[H:]       skip_in NULL in the first layer
+ * amp_ns2_layer_create: conv_weight [2H, H, 3], conv_bias [2H] (NULL = zeros), out_weight [2H, H], out_bias [2H] (NULL = zeros), host fp32.
+ * H a multiple of 64 in [128, 512], dilation 1 .. 8 (padding = dilation); anything else AMP_ERR_UNSUPPORTED.  Any T >= 1.
+ * A handle keeps the arithmetic it was created under.  f16x3: two launches -- the gated GEMM over K = 3H (the [2H, T] pre-activation never
+ * goes to memory; z [B, H, T] goes to the workspace) and out_proj on the pointwise GEMM kernel with a residual | skip epilogue; staged
+ * operands report to the op-level range flag (amp_range_check).  AMP_PRECISION_F32: the exact conv between element-wise launches (five
+ * launches; not the hot path).  ws_dev: amp_ns2_layer_workspace_bytes(h, B, T) bytes, not overlapping any tensor.
+ * x_out may be x (in place) or must not overlap it; skip_out may be skip_in; skip_out must not overlap x or x_out.
+ * AMP_ERR_INVALID with a message: a NULL handle / x / dconst / cterm / x_out / skip_out / workspace, B or T < 1, B > 65535, a stride below its
+ * extent, a workspace too small, the overlaps above. */
+typedef struct amp_ns2_layer amp_ns2_layer;
+int amp_ns2_layer_create(int hidden, int dilation, const float* conv_weight_host, const float* conv_bias_host, const float* out_weight_host,
+                         const float* out_bias_host, amp_ns2_layer** out);
+int amp_ns2_layer_precision(const amp_ns2_layer* h);
+size_t amp_ns2_layer_workspace_bytes(const amp_ns2_layer* h, int B, int T);
+int amp_ns2_layer_forward(const amp_ns2_layer* h, const float* x_dev, const float* dconst_dev, long long dconst_batch_stride, const float* cterm_dev,
+                          long long cterm_batch_stride, const float* film_dev, const float* skip_in_dev, int B, int T, float* x_out_dev,
+                          float* skip_out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+void amp_ns2_layer_destroy(amp_ns2_layer* h);
+
+/* The element-wise tail of Diffusion.cal_dxt (diffusion.py:72-82) and the solver's update in one launch, over n elements:
+ *     mean  = x0_pred * mean_scale                      mean_scale = exp(-0.5 * cum_beta / sigma^2)
+ *     logp  = -(x_eval - mean) / (variance + 1e-8)      variance   = sigma^2 * (1 - exp(-cum_beta / sigma^2))
+ *     dxt   = (-0.5 * h_beta) * (logp + x_eval * inv_sigma2)           h_beta = h * beta_t
+ *     out   = x_base - dxt                              midpoint_half != 0: out = 0.5 * ((x_base - dxt) + x_base), the midpoint solver's x_mid
+ * The caller forms the four scalars as the reference does (fp32, on a one-element tensor) and passes them by value.  euler: x_eval = x_base =
+ * xt.  midpoint: first x_eval = x_base = xt with midpoint_half = 1, then x_eval = x_mid, x_base = xt.  Plain fp32, one rounding per
+ * operation; out may be any of the inputs (element-wise) or must not overlap them.
+ * AMP_ERR_INVALID with a message: a NULL pointer, n < 1, a NaN scalar, a partial overlap; more than 2^31 - 1 workgroups AMP_ERR_UNSUPPORTED. */
+int amp_ns2_ode_step(const float* x_eval_dev, const float* x0_pred_dev, const float* x_base_dev, long long n, float mean_scale, float variance,
+                     float h_beta, float inv_sigma2, int midpoint_half, float* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
