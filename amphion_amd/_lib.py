@@ -217,6 +217,12 @@ _SIGNATURES = {
     "amp_mh_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_cross_attention": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                     c_void_p, c_void_p]),
+    "amp_prefix_attention": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                     c_void_p]),
+    "amp_pw_forward_vec_ln": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "amp_pw_forward_vec_ln_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "amp_embed_pos": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "amp_ns2_layer_create": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "amp_ns2_layer_precision": (c_int, [c_void_p]),
     "amp_ns2_layer_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),

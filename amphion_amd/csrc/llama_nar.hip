@@ -4,6 +4,7 @@
 //     amp_rope_attention_causal the same kernel with its compile-time causal flag: the prefill of the autoregressive transformer (llama_ar.hip)
 //     amp_mh_attention          the same kernel with its compile-time rotation flag off, head dimension 128: the FFT block of FastSpeech2 / JETS
 //     amp_cross_attention       the same, head dimension 64, with query and key extents and batch strides apart: every attention of NaturalSpeech2
+//     amp_prefix_attention      causal without rotation, head dimension 64, with a run-time prefix every query sees: the prefill of VALL-E's AR stage
 //     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
 //     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
 // Everything is channel-first [B, C, T] fp32.  Deterministic: no atomics on data (the attention kernel ORs the op-level range flag).
@@ -50,6 +51,7 @@ struct AttnArgs {
     int H, Tq, Tk;                 // queries (rows of q and out are Tq apart) and keys (rows of k and v are Tk apart); equal except for amp_cross_attention
     float c;                       // scale / 256: un-does the two x16 of the staged operands (a power of two at DK = 64 only: one rounding at 96)
     unsigned* range_flag;
+    int prefix;                    // CAUSAL && !ROPE only (amp_prefix_attention): keys [0, prefix) are visible to every query
 };
 
 // DK = 64 or 96 (with rotation), 128 (without).  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
@@ -58,6 +60,8 @@ struct AttnArgs {
 // CAUSAL (amp_rope_attention_causal): key j is visible to query i iff j <= i (and the key mask admits it).  The workgroup walks the key
 // tiles up to the one that holds its last query; in a tile that reaches beyond the wave's first query the comparison joins the validity
 // select below.  A key beyond the query is staged like any other and meets p = exp2(-inf) = 0: it contributes exactly 0.
+// CAUSAL && !ROPE (amp_prefix_attention, DK = 64) is the prefix-LM rule: key j is visible to query i iff j < a.prefix || j <= i.  The workgroup
+// walks up to the tile of max(its last query, prefix - 1) and the prefix joins the same comparison; prefix = 0 is the causal rule, prefix = T full attention.
 // ROPE = false (amp_mh_attention, fastspeech.hip's FFT block): no rotation -- Q' = q and K' = k, cs / sn are never read; the channel pairs
 // (i, i + HALF) stay the staging pattern, nothing more.  DK = 128 is built in this form only: its planes (32 KB of K', 34 KB of V) are
 // beyond what a static __shared__ array may hold, so they are the launch's dynamic LDS (attn_lds_bytes); DK <= 96 keeps the static arrays.
@@ -157,7 +161,8 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
 
     int nkt = (T + AT_TK - 1) / AT_TK;
     if (CAUSAL) {                                          // uniform over the workgroup: the tile of its last query
-        const int qlast = (int)blockIdx.x * AT_TQ + AT_TQ - 1;
+        int qlast = (int)blockIdx.x * AT_TQ + AT_TQ - 1;
+        if constexpr (!ROPE) qlast = qlast > a.prefix - 1 ? qlast : a.prefix - 1;
         nkt = (qlast < T ? qlast : T - 1) / AT_TK + 1;
     }
     const int qw0 = (int)blockIdx.x * AT_TQ + 32 * w;      // the wave's first query
@@ -243,7 +248,12 @@ __global__ __launch_bounds__(64 * AT_NW) void rope_attention_kernel(AttnArgs a) 
                 float s = S[rb][0][r] * a.c;
                 if (!all_valid) s = ((mw >> acc_row(r)) & 1u) ? s : -INFINITY;
                 if (CAUSAL) {
-                    if (diag) s = acc_row(r, hi, kt * AT_TK + 32 * rb) <= tq ? s : -INFINITY;
+                    if constexpr (ROPE) {
+                        if (diag) s = acc_row(r, hi, kt * AT_TK + 32 * rb) <= tq ? s : -INFINITY;
+                    } else {
+                        const int key = acc_row(r, hi, kt * AT_TK + 32 * rb);
+                        if (diag) s = (key <= tq || key < a.prefix) ? s : -INFINITY;
+                    }
                 }
                 sv[rb][r] = s;
                 mx = __builtin_fmaxf(mx, s);
@@ -397,14 +407,17 @@ __global__ __launch_bounds__(256) void attn_one_key_kernel(const float* __restri
 
 using namespace amp;
 
-// the four attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false: amp_mh_attention at
-// dk = 128 and, with `cross`, amp_cross_attention at dk = 64; cos / sin unused).  Tq != Tk and q_stride != kv_stride come from amp_cross_attention only.
+// the five attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false: amp_mh_attention at
+// dk = 128, with `cross` amp_cross_attention at dk = 64, with `causal` amp_prefix_attention at dk = 64 and its `prefix`; cos / sin unused).  Tq != Tk and
+// q_stride != kv_stride come from amp_cross_attention only.
 static int rope_attention_run(const char* who, bool causal, bool rope, bool cross, const float* q_dev, long long q_stride, const float* k_dev, const float* v_dev,
                               long long kv_stride, const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk,
-                              int Tq, int T, float scale, float* out_dev, void* stream) {
+                              int Tq, int T, float scale, float* out_dev, void* stream, int prefix = 0) {
+    const bool pfx = causal && !rope;
     if (!q_dev || !k_dev || !v_dev || (rope && (!cos_dev || !sin_dev)) || !out_dev) { set_error("%s: null argument", who); return AMP_ERR_INVALID; }
     if (rope && dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
-    if (!rope && !cross && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
+    if (pfx && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
+    if (!rope && !cross && !pfx && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
     if (cross && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
     if (cross) {
         if (B < 1 || H < 1 || Tq < 1 || T < 1) { set_error("%s: B=%d H=%d Tq=%d Tk=%d", who, B, H, Tq, T); return AMP_ERR_INVALID; }
@@ -413,6 +426,7 @@ static int rope_attention_run(const char* who, bool causal, bool rope, bool cros
         if (B < 1 || H < 1 || T < 1) { set_error("%s: B=%d H=%d T=%d", who, B, H, T); return AMP_ERR_INVALID; }
         if (T > AT_MAX_T) { set_error("%s: T=%d is beyond %d", who, T, AT_MAX_T); return AMP_ERR_INVALID; }
     }
+    if (pfx && (prefix < 0 || prefix > T)) { set_error("%s: prefix=%d is outside [0, T=%d]", who, prefix, T); return AMP_ERR_INVALID; }
     if ((long long)B * H > 65535) { set_error("%s: B*H=%lld is beyond the grid (65535)", who, (long long)B * H); return AMP_ERR_INVALID; }
     if (!(scale > 0.f) || !(scale < 1e30f)) { set_error("%s: scale=%g", who, (double)scale); return AMP_ERR_INVALID; }
     if (kv_stride == 0) kv_stride = (long long)H * dk * T;
@@ -458,9 +472,17 @@ static int rope_attention_run(const char* who, bool causal, bool rope, bool cros
     a.H = H; a.Tq = Tq; a.Tk = T;
     a.c = scale * (1.0f / 256.f);
     a.range_flag = range_flag_for_current_device();
+    a.prefix = prefix;
     const dim3 grid((unsigned)((Tq + AT_TQ - 1) / AT_TQ), (unsigned)(B * H));
     if (rope) note_kernel("rope_attention_kernel", dk, causal ? 1 : 0);
-    else note_kernel("rope_attention_kernel", dk, 0, 0);
+    else note_kernel("rope_attention_kernel", dk, pfx ? 1 : 0, 0);
+    if (pfx) {
+        note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * ((double)T * prefix + 0.5 * (double)(T - prefix) * (T - prefix)) / 1e9,
+                  16.0 * (double)B * H * dk * T / 1e6, "prefix attention B=%d H=%d dk=%d T=%d prefix=%d mask=%d", B, H, dk, T, prefix, key_mask_dev ? 1 : 0);
+        hipLaunchKernelGGL((rope_attention_kernel<64, true, false>), grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+        AMP_HIP(hipGetLastError());
+        return AMP_OK;
+    }
     if (cross) {
         note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)Tq * T / 1e9, 8.0 * (double)B * H * dk * ((double)Tq + T) / 1e6,
                   "cross attention B=%d H=%d dk=%d Tq=%d Tk=%d mask=%d", B, H, dk, Tq, T, key_mask_dev ? 1 : 0);
@@ -510,6 +532,12 @@ int amp_cross_attention(const float* q_dev, long long q_batch_stride, const floa
                         const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream) {
     return rope_attention_run("amp_cross_attention", false, false, true, q_dev, q_batch_stride, k_dev, v_dev, kv_batch_stride, nullptr, nullptr, key_mask_dev, B,
                               H, dk, Tq, Tk, scale, out_dev, stream);
+}
+
+int amp_prefix_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const unsigned char* key_mask_dev, int B,
+                         int H, int dk, int T, int prefix, float scale, float* out_dev, void* stream) {
+    return rope_attention_run("amp_prefix_attention", true, false, false, q_dev, batch_stride, k_dev, v_dev, batch_stride, nullptr, nullptr, key_mask_dev, B, H, dk,
+                              T, T, scale, out_dev, stream, prefix);
 }
 
 int amp_rms_norm_c_adaptive(const float* x_dev, const float* w_dev, long long w_batch_stride, int B, int C, int T, float eps, float* y_dev,

@@ -206,7 +206,9 @@ extern "C" {
 // amp_fs2_durations, amp_bucketize_embed_add, amp_layer_norm_c_head (fastspeech.hip)
 // 157 (additive): NaturalSpeech2 inference -- amp_cross_attention (llama_nar.hip's kernel without rotation at head dimension 64, separate query and
 // key extents), amp_ns2_layer_* (ns2_layer_f16x3.hip) and amp_ns2_ode_step (ns2.hip)
-int amp_version(void) { return 157; }
+// 158 (additive): VALL-E inference -- amp_prefix_attention (llama_nar.hip's causal kernel without rotation, with a run-time prefix) and
+// amp_pw_forward_vec_ln, amp_embed_pos (valle.hip)
+int amp_version(void) { return 158; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

@@ -959,3 +959,109 @@ def ns2_ode_step(x_eval, x0_pred, x_base, mean_scale, variance, h_beta, inv_sigm
         _lib.check(_lib.lib().amp_ns2_ode_step(_ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), ts[0].numel(), float(mean_scale), float(variance), float(h_beta),
                                                float(inv_sigma2), 1 if midpoint_half else 0, _ptr(out), _stream(out)))
     return out
+
+
+# ---- VALL-E inference (csrc/valle.hip; the prefill attention is llama_nar.hip's causal kernel without rotation) ----------------
+def prefix_attention(q, k, v, n_heads, prefix, key_mask=None, scale=None):
+    """Self-attention without rotation at head dimension 64 under the prefix-LM rule (``amp_prefix_attention``): key j is visible to query i
+    iff ``j < prefix or j <= i`` and the key mask admits it.
+
+    q, k, v [B, H*dk, T] channel-first: contiguous tensors, or the three row blocks of one stacked [B, 3*H*dk, T] GEMM output (read in
+    place).  0 <= prefix <= T (0: causal, T: full attention).  key_mask [B, T] bool / uint8, 1 = VALID; None = all valid.  scale defaults to
+    1 / sqrt(dk).  -> [B, H*dk, T].  Under the "f32" precision the same formula runs as ``scaled_dot_product_attention`` in torch (not the hot path)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _f32_dev(t, name, "prefix_attention")
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or k.device != q.device or v.device != q.device:
+        raise ValueError(f"prefix_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    B, C, T = q.shape
+    H, prefix = int(n_heads), int(prefix)
+    if H < 1 or C % H:
+        raise ValueError(f"prefix_attention: {C} channels do not divide into {H} heads")
+    dk = C // H
+    if dk != 64:
+        raise ValueError(f"prefix_attention: head dimension {dk} is not covered (dk = 64)")
+    if B < 1 or T < 1:
+        raise ValueError(f"prefix_attention: empty input {tuple(q.shape)}")
+    if not 0 <= prefix <= T:
+        raise ValueError(f"prefix_attention: prefix={prefix} is outside [0, {T}]")
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
+            raise ValueError(f"prefix_attention: key_mask must be a {(B, T)} tensor on {q.device}")
+        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
+            key_mask = (key_mask != 0).to(torch.uint8)
+        key_mask = key_mask.contiguous()
+    scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
+    with _lib.on_device(q.device):
+        if _lib.get_precision() == "f32":
+            j = torch.arange(T, device=q.device)
+            m = ((j[None, :] < prefix) | (j[None, :] <= j[:, None]))[None, None]
+            if key_mask is not None:
+                m = m & key_mask.bool()[:, None, None, :]
+            o = torch.nn.functional.scaled_dot_product_attention(*(t.reshape(B, H, dk, T).transpose(2, 3) for t in (q, k, v)), attn_mask=m,
+                                                                 scale=scale)
+            return o.transpose(2, 3).reshape(B, C, T).contiguous()
+        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
+        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            bstride = C * T
+        out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
+        _lib.check(_lib.lib().amp_prefix_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(key_mask), B, H, dk, T, prefix, scale, _ptr(out),
+                                                   _stream(q)))
+    return out
+
+
+def pw_forward_vec_ln(h, cout, x, ln_gamma=None, ln_beta=None, eps=1e-5, relu=False, gamma=None, res=None, out=None):
+    """``amp_pw_forward_vec_ln``: ``epi(W n(x) + b)`` of the ``amp_pw`` handle ``h`` on x [B, cin, 1] (B <= 8; contiguous, or a row block of a
+    wider [B, C, 1] tensor) -> [B, cout, 1].  n = LayerNorm over the cin channels with ``ln_gamma`` / ``ln_beta`` [cin] (both None: n(x) = x);
+    epi = bias, bias -> ReLU (``relu``), or ``res + gamma * (.)`` (``res`` and ``gamma`` [cout]; not with ``relu``)."""
+    _f32_dev(x, "x", "pw_forward_vec_ln")
+    if x.dim() != 3 or x.shape[2] != 1 or x.numel() == 0:
+        raise ValueError(f"pw_forward_vec_ln: expected a [B, cin, 1] input, got {tuple(x.shape)}")
+    B, cin = x.shape[0], x.shape[1]
+    if (ln_gamma is None) != (ln_beta is None):
+        raise ValueError("pw_forward_vec_ln: ln_gamma and ln_beta come together")
+    for t, name in ((ln_gamma, "ln_gamma"), (ln_beta, "ln_beta")):
+        if t is not None and (_f32_dev(t, name, "pw_forward_vec_ln").numel() != cin or t.device != x.device or not t.is_contiguous()):
+            raise ValueError(f"pw_forward_vec_ln: {name} must hold {cin} contiguous values on {x.device}")
+    if (res is None) != (gamma is None) or (res is not None and relu):
+        raise ValueError("pw_forward_vec_ln: the residual epilogue takes res and gamma, and no relu")
+    if (cin > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < cin):
+        x = x.contiguous()
+    xbs = int(x.stride(0)) if B > 1 else cin
+    if out is None:
+        out = torch.empty((B, int(cout), 1), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        L_ = _lib.lib()
+        nbytes = L_.amp_pw_forward_vec_ln_workspace_bytes(h, B)
+        ws = _workspace(x.device, nbytes)
+        _lib.check(L_.amp_pw_forward_vec_ln(h, _ptr(x), xbs, B, _ptr(ln_gamma), _ptr(ln_beta), float(eps), 1 if relu else 0, _ptr(gamma), _ptr(res),
+                                            _ptr(out), _ptr(ws), nbytes, _stream(x)))
+    return out
+
+
+def embed_pos(tokens, weight, pe, pos0, alpha, x_scale=1.0, check=True):
+    """``amp_embed_pos``: ``weight[tokens] * x_scale + alpha * pe[pos0 : pos0 + T]`` channel-first.  tokens int64 [B, T]; weight [rows, D];
+    pe [pe_rows, D]; alpha a one-element fp32 tensor on the device.  -> y [B, D, T].  An id outside [0, rows) raises ``AmpError``
+    (AMP_ERR_INVALID) -- here, or with ``check=False`` at the caller's ``embed_sum_check`` (the check synchronises; a decode loop runs it
+    once behind its steps)."""
+    weight, pe, alpha = (_f32_dev(t.detach(), n, "embed_pos") for t, n in ((weight, "weight"), (pe, "pe"), (alpha, "alpha")))
+    if not isinstance(tokens, torch.Tensor) or tokens.dtype != torch.int64 or tokens.dim() != 2 or tokens.numel() == 0 or tokens.device != weight.device:
+        raise ValueError(f"embed_pos: tokens must be a non-empty int64 [B, T] tensor on {weight.device}")
+    if weight.dim() != 2 or pe.dim() != 2 or pe.shape[1] != weight.shape[1] or alpha.numel() != 1 or pe.device != weight.device or alpha.device != weight.device:
+        raise ValueError(f"embed_pos: weight [rows, D], pe [pe_rows, D] and a one-element alpha on one device, got {tuple(weight.shape)}, {tuple(pe.shape)}, "
+                         f"{tuple(alpha.shape)}")
+    B, T = tokens.shape
+    rows, D = weight.shape
+    pos0 = int(pos0)
+    if pos0 < 0 or pos0 + T > pe.shape[0]:
+        raise ValueError(f"embed_pos: positions [{pos0}, {pos0 + T}) are beyond a table of {pe.shape[0]} rows")
+    tokens, weight, pe = tokens.contiguous(), weight.contiguous(), pe.contiguous()
+    flag = _embed_sum_flag(weight.device)
+    y = torch.empty((B, D, T), dtype=torch.float32, device=weight.device)
+    with _lib.on_device(weight.device):
+        _lib.check(_lib.lib().amp_embed_pos(_ptr(tokens), _ptr(weight), rows, D, _ptr(pe), pe.shape[0], pos0, float(x_scale), _ptr(alpha), B, T, _ptr(y),
+                                            _ptr(flag), _stream(y)))
+        if check:
+            _lib.check(_lib.lib().amp_embed_sum_check(_ptr(flag), _stream(y)))
+    return y

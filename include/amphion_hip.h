@@ -107,7 +107,9 @@ typedef struct amp_gen amp_gen;
  * 156 (additive): amp_mh_attention (head dimension 128, no rotation), amp_fs2_durations, amp_bucketize_embed_add and amp_layer_norm_c_head
  * (FastSpeech2 / JETS inference);
  * 157 (additive): amp_cross_attention (head dimension 64, no rotation, separate query and key lengths), amp_ns2_layer_* and amp_ns2_ode_step
- * (NaturalSpeech2 inference). */
+ * (NaturalSpeech2 inference);
+ * 158 (additive): amp_prefix_attention (causal without rotation at head dimension 64, with a run-time prefix), amp_pw_forward_vec_ln
+ * (+ _workspace_bytes) and amp_embed_pos (VALL-E inference). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -1137,6 +1139,50 @@ void amp_ns2_layer_destroy(amp_ns2_layer* h);
  * AMP_ERR_INVALID with a message: a NULL pointer, n < 1, a NaN scalar, a partial overlap; more than 2^31 - 1 workgroups AMP_ERR_UNSUPPORTED. */
 int amp_ns2_ode_step(const float* x_eval_dev, const float* x0_pred_dev, const float* x_base_dev, long long n, float mean_scale, float variance,
                      float h_beta, float inv_sigma2, int midpoint_half, float* out_dev, void* stream);
+
+/* ---- VALL-E inference (csrc/valle.hip, csrc/llama_nar.hip; models/tts/valle/valle.py, modules/transformer/transformer.py,
+ * modules/norms/norm.py).  Channel-first [B, C, T] fp32.  Deterministic, no atomics on data, no allocation and no synchronisation; every
+ * argument is judged on the host before anything is launched. ---- */
+
+/* Self-attention WITHOUT rotation at head dimension 64 under the prefix-LM rule, in one launch: key j is visible to query i iff
+ * (j < prefix || j <= i) AND the key mask admits it -- text columns [0, prefix) see all text and no audio, audio columns see all text and
+ * the audio up to themselves.  prefix = 0 is the plain causal rule, prefix = T full attention (then bit for bit amp_cross_attention at
+ * Tq = Tk).  This is amp_rope_attention_causal's kernel with its rotation compiled out, and everything that entry point states holds here:
+ * q, k, v [B, H*dk, T] with rows T apart and ONE batch stride (0 = dense; the three row blocks of a stacked q | k | v GEMM output are read
+ * in place), out dense and not overlapping them; key_mask [B, T] bytes, 1 = valid, or NULL; a query block walks the key tiles up to the one
+ * that holds max(its last query, prefix - 1); a hidden key is staged like any other and meets p = 0: it contributes exactly 0 whatever
+ * finite value it holds, and a masked key whatever it holds; a query without a visible valid key gets a NaN column; split-f16 MFMA products
+ * with an fp32 online softmax whatever amp_set_precision says; q, k, v take part in the op-level range guard; T = 1 is a copy of v.
+ * AMP_ERR_INVALID with a message: a NULL pointer (key_mask excepted), dk other than 64, B, H or T < 1, T > 32768, B*H > 65535, prefix
+ * outside [0, T], batch_stride below H*dk*T, a non-positive or non-finite scale, out overlapping q / k / v. */
+int amp_prefix_attention(const float* q_dev, const float* k_dev, const float* v_dev, long long batch_stride, const unsigned char* key_mask_dev, int B,
+                         int H, int dk, int T, int prefix, float scale, float* out_dev, void* stream);
+
+/* amp_pw_forward_vec with the LayerNorm of its input folded into the staging of x and a ReLU epilogue beside the residual one:
+ *     y = epi( W n(x) + b ),     n(x) = (x - mean) * (1 / sqrtf(var + eps)) * ln_gamma + ln_beta     over the cin channels of each item
+ * (biased variance of the centred values, two passes; n(x) = x when ln_gamma and ln_beta are NULL), epi = bias, bias -> ReLU (relu != 0), or
+ * res + gamma (.) (.) (gamma and res given; y may alias res).  Same handle, packed weights, grid, K slices, workspace size and order of
+ * every sum as amp_pw_forward_vec: with ln_gamma = NULL and relu = 0 the result is that entry point's, bit for bit.  Every workgroup forms
+ * the statistics of the whole row(s) itself, in an order fixed by cin alone, before it stages its own K slice: all of them hold the same
+ * bits.  x is never split, so there is no range guard.  A constant row (variance 0) gives finite values (eps > 0).
+ * AMP_ERR_INVALID with a message: a NULL handle / x / y / workspace, B outside [1, 8], one of ln_gamma / ln_beta or of gamma / res without
+ * the other, the LayerNorm form at cin > 4096, a negative or non-finite eps, relu beside res, x_batch_stride below cin, a workspace too
+ * small, x, y and the workspace overlapping, res overlapping y without being y. */
+int amp_pw_forward_vec_ln(const amp_pw* h, const float* x_dev, long long x_batch_stride, int B, const float* ln_gamma_dev, const float* ln_beta_dev,
+                          float eps, int relu, const float* gamma_dev, const float* res_dev, float* y_dev, float* workspace_dev,
+                          size_t workspace_bytes, void* stream);
+size_t amp_pw_forward_vec_ln_workspace_bytes(const amp_pw* h, int B);
+
+/* TokenEmbedding followed by SinePositionalEmbedding from a running position, channel-first:
+ *     y[b, :, t] = weight[tokens[b, t], :] * x_scale + alpha * pe[pos0 + t, :]
+ * tokens int64 [B, T]; weight [rows, D]; pe [pe_rows, D], the table the module builds (position_embedding.py:43-48), uploaded once; alpha ONE
+ * fp32 value on the device (the module's parameter, read in place); y [B, D, T].  T = the prompt once, then T = 1 per decode step.  The two
+ * products and the add are three fp32 roundings, as torch evaluates the expression: no fma.  An id outside [0, rows) reads row 0 instead (never
+ * out of bounds) and sets *flag_dev, a zero-initialised 32-bit word of the caller's that amp_embed_sum_check reads and clears.
+ * AMP_ERR_INVALID with a message: a NULL pointer, rows, D, B, T or pe_rows < 1, pos0 < 0, pos0 + T > pe_rows; B or ceil(D / 64) beyond 65535
+ * AMP_ERR_UNSUPPORTED. */
+int amp_embed_pos(const long long* tokens_dev, const float* weight_dev, int rows, int D, const float* pe_dev, int pe_rows, int pos0, float x_scale,
+                  const float* alpha_dev, int B, int T, float* y_dev, unsigned* flag_dev, void* stream);
 
 #ifdef __cplusplus
 }
