@@ -290,6 +290,18 @@ _SIGNATURES = {
     "amp_mel_init": (c_int, []),
     "amp_mel_forward_ragged": (c_int, [POINTER(amp_mel_desc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "amp_mel_backward": (c_int, [POINTER(amp_mel_desc), c_void_p, c_int, c_int] + [c_void_p] * 11),
+    "amp_conv2d_create": (c_int, [c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "amp_conv2d_precision": (c_int, [c_void_p]),
+    "amp_conv2d_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "amp_conv2d_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "amp_conv2d_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "amp_conv2d_destroy": (None, [c_void_p]),
+    "amp_group_norm_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "amp_group_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "amp_cross_attention_hd": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                       c_void_p, c_void_p]),
+    "amp_geglu": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "amp_mel_forward": (c_int, [POINTER(amp_mel_desc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 

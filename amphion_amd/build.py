@@ -48,7 +48,7 @@ def _units():
              ("dsconv_f16x3.hip", "dsconv_f16x3.o", []), ("llama_nar.hip", "llama_nar.o", []),
              ("maskgct.hip", "maskgct.o", []), ("llama_ar.hip", "llama_ar.o", []), ("fastspeech.hip", "fastspeech.o", []),
              ("ns2_layer_f16x3.hip", "ns2_layer_f16x3.o", []), ("ns2.hip", "ns2.o", []),
-             ("valle.hip", "valle.o", [])]
+             ("valle.hip", "valle.o", []), ("conv2d_f16x3.hip", "conv2d_f16x3.o", []), ("tta.hip", "tta.o", [])]
     for kt in CONV_TAPS:
         units.append(("conv_mfma.hip", f"conv_mfma_kt{kt}.o", [f"-DAMP_KT={kt}"]))
         units.append(("conv_f16x3.hip", f"conv_f16x3_kt{kt}.o", [f"-DAMP_KT={kt}"]))

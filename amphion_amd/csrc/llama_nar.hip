@@ -4,6 +4,7 @@
 //     amp_rope_attention_causal the same kernel with its compile-time causal flag: the prefill of the autoregressive transformer (llama_ar.hip)
 //     amp_mh_attention          the same kernel with its compile-time rotation flag off, head dimension 128: the FFT block of FastSpeech2 / JETS
 //     amp_cross_attention       the same, head dimension 64, with query and key extents and batch strides apart: every attention of NaturalSpeech2
+//     amp_cross_attention_hd    the same at head dimension 32 (a new instantiation), 64 or 128 (amp_mh_attention's): AudioLDM's spatial transformer
 //     amp_prefix_attention      causal without rotation, head dimension 64, with a run-time prefix every query sees: the prefill of VALL-E's AR stage
 //     amp_rms_norm_c_adaptive   LlamaAdaptiveRMSNorm (llama_nar.py:32-50) over the channel axis, one weight row per item
 //     amp_silu / amp_swiglu     nn.SiLU and LlamaMLP's silu(gate) * up on the stacked gate | up GEMM output
@@ -54,7 +55,7 @@ struct AttnArgs {
     int prefix;                    // CAUSAL && !ROPE only (amp_prefix_attention): keys [0, prefix) are visible to every query
 };
 
-// DK = 64 or 96 (with rotation), 128 (without).  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
+// DK = 64 or 96 (with rotation), 32 or 128 (without).  HALF = DK / 2 is the rotate-half distance (16 NP channels: Q' fragment s pairs with s + NP), NF = DK / 16 the k-steps of
 // S, ND = DK / 32 the row blocks of O, HO = DK / 16 the channel octets per half: wave w stages octets w, w + 4, ... < HO with their partners
 // (at DK = 96 waves 0 and 1 take two octet pairs, waves 2 and 3 one).
 // CAUSAL (amp_rope_attention_causal): key j is visible to query i iff j <= i (and the key mask admits it).  The workgroup walks the key
@@ -407,10 +408,10 @@ __global__ __launch_bounds__(256) void attn_one_key_kernel(const float* __restri
 
 using namespace amp;
 
-// the five attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false: amp_mh_attention at
-// dk = 128, with `cross` amp_cross_attention at dk = 64, with `causal` amp_prefix_attention at dk = 64 and its `prefix`; cos / sin unused).  Tq != Tk and
-// q_stride != kv_stride come from amp_cross_attention only.
-static int rope_attention_run(const char* who, bool causal, bool rope, bool cross, const float* q_dev, long long q_stride, const float* k_dev, const float* v_dev,
+// the six attention entries: `who` names the entry in the messages, `causal` and `rope` pick the instantiation (rope = false: amp_mh_attention at
+// dk = 128, with `cross` = 1 amp_cross_attention at dk = 64, with `cross` = 2 amp_cross_attention_hd at dk = 32, 64 or 128, with `causal` amp_prefix_attention at
+// dk = 64 and its `prefix`; cos / sin unused).  Tq != Tk and q_stride != kv_stride come from the two cross entries only.
+static int rope_attention_run(const char* who, bool causal, bool rope, int cross, const float* q_dev, long long q_stride, const float* k_dev, const float* v_dev,
                               long long kv_stride, const float* cos_dev, const float* sin_dev, const unsigned char* key_mask_dev, int B, int H, int dk,
                               int Tq, int T, float scale, float* out_dev, void* stream, int prefix = 0) {
     const bool pfx = causal && !rope;
@@ -418,7 +419,8 @@ static int rope_attention_run(const char* who, bool causal, bool rope, bool cros
     if (rope && dk != 64 && dk != 96) { set_error("%s: head dimension %d is not covered (dk = 64 or 96)", who, dk); return AMP_ERR_INVALID; }
     if (pfx && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
     if (!rope && !cross && !pfx && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 128)", who, dk); return AMP_ERR_INVALID; }
-    if (cross && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
+    if (cross == 1 && dk != 64) { set_error("%s: head dimension %d is not covered (dk = 64)", who, dk); return AMP_ERR_INVALID; }
+    if (cross == 2 && dk != 32 && dk != 64 && dk != 128) { set_error("%s: head dimension %d is not covered (dk = 32, 64 or 128)", who, dk); return AMP_ERR_INVALID; }
     if (cross) {
         if (B < 1 || H < 1 || Tq < 1 || T < 1) { set_error("%s: B=%d H=%d Tq=%d Tk=%d", who, B, H, Tq, T); return AMP_ERR_INVALID; }
         if (Tq > AT_MAX_T || T > AT_MAX_T) { set_error("%s: Tq=%d / Tk=%d is beyond %d", who, Tq, T, AT_MAX_T); return AMP_ERR_INVALID; }
@@ -486,7 +488,15 @@ static int rope_attention_run(const char* who, bool causal, bool rope, bool cros
     if (cross) {
         note_work((unsigned long long)grid.x * grid.y, 4.0 * 3.0 * (double)B * H * dk * (double)Tq * T / 1e9, 8.0 * (double)B * H * dk * ((double)Tq + T) / 1e6,
                   "cross attention B=%d H=%d dk=%d Tq=%d Tk=%d mask=%d", B, H, dk, Tq, T, key_mask_dev ? 1 : 0);
-        hipLaunchKernelGGL((rope_attention_kernel<64, false, false>), grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+        if (dk == 128) {                                   // amp_mh_attention's instantiation and LDS plan, with the extents apart
+            constexpr size_t lds = attn_lds_bytes<128>();
+            AMP_HIP((ensure_dynamic_lds<rope_attention_kernel<128, false, false>>(lds)));
+            hipLaunchKernelGGL((rope_attention_kernel<128, false, false>), grid, dim3(64 * AT_NW), lds, (hipStream_t)stream, a);
+        } else if (dk == 32) {
+            hipLaunchKernelGGL((rope_attention_kernel<32, false, false>), grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+        } else {
+            hipLaunchKernelGGL((rope_attention_kernel<64, false, false>), grid, dim3(64 * AT_NW), 0, (hipStream_t)stream, a);
+        }
         AMP_HIP(hipGetLastError());
         return AMP_OK;
     }
@@ -530,7 +540,13 @@ int amp_mh_attention(const float* q_dev, const float* k_dev, const float* v_dev,
 
 int amp_cross_attention(const float* q_dev, long long q_batch_stride, const float* k_dev, const float* v_dev, long long kv_batch_stride,
                         const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream) {
-    return rope_attention_run("amp_cross_attention", false, false, true, q_dev, q_batch_stride, k_dev, v_dev, kv_batch_stride, nullptr, nullptr, key_mask_dev, B,
+    return rope_attention_run("amp_cross_attention", false, false, 1, q_dev, q_batch_stride, k_dev, v_dev, kv_batch_stride, nullptr, nullptr, key_mask_dev, B,
+                              H, dk, Tq, Tk, scale, out_dev, stream);
+}
+
+int amp_cross_attention_hd(const float* q_dev, long long q_batch_stride, const float* k_dev, const float* v_dev, long long kv_batch_stride,
+                           const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream) {
+    return rope_attention_run("amp_cross_attention_hd", false, false, 2, q_dev, q_batch_stride, k_dev, v_dev, kv_batch_stride, nullptr, nullptr, key_mask_dev, B,
                               H, dk, Tq, Tk, scale, out_dev, stream);
 }
 

@@ -208,7 +208,9 @@ extern "C" {
 // key extents), amp_ns2_layer_* (ns2_layer_f16x3.hip) and amp_ns2_ode_step (ns2.hip)
 // 158 (additive): VALL-E inference -- amp_prefix_attention (llama_nar.hip's causal kernel without rotation, with a run-time prefix) and
 // amp_pw_forward_vec_ln, amp_embed_pos (valle.hip)
-int amp_version(void) { return 158; }
+// 159 (additive): AudioLDM text-to-audio -- amp_conv2d_* (conv2d_f16x3.hip), amp_group_norm_stats, amp_group_norm, amp_geglu (tta.hip) and
+// amp_cross_attention_hd: amp_cross_attention at head dimensions 32 and 128 beside 64 (llama_nar.hip)
+int amp_version(void) { return 159; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {

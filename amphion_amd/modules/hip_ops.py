@@ -833,6 +833,11 @@ def cross_attention(q, k, v, n_heads, key_mask=None, scale=None):
     place (k | v of one tensor; for self-attention q | k | v of one tensor).  key_mask [B, Tk] bool / uint8, 1 = VALID, any pattern, at least
     one valid key per item; None = all valid.  scale defaults to 1 / sqrt(dk).  -> [B, H*dk, Tq].  Under the "f32" precision the same formula
     runs as ``scaled_dot_product_attention`` in torch (not the hot path)."""
+    return _cross_attention("amp_cross_attention", (64,), q, k, v, n_heads, key_mask, scale)
+
+
+def _cross_attention(entry, dks, q, k, v, n_heads, key_mask, scale):
+    """``cross_attention`` through the C entry ``entry``, which covers the head dimensions ``dks``"""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         _f32_dev(t, name, "cross_attention")
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[:2] != k.shape[:2] or k.device != q.device or v.device != q.device:
@@ -844,8 +849,8 @@ def cross_attention(q, k, v, n_heads, key_mask=None, scale=None):
     if H < 1 or C % H:
         raise ValueError(f"cross_attention: {C} channels do not divide into {H} heads")
     dk = C // H
-    if dk != 64:
-        raise ValueError(f"cross_attention: head dimension {dk} is not covered (dk = 64)")
+    if dk not in dks:
+        raise ValueError(f"cross_attention: head dimension {dk} is not covered (dk = {' / '.join(map(str, dks))})")
     if B < 1 or Tq < 1 or Tk < 1:
         raise ValueError(f"cross_attention: empty input {tuple(q.shape)}, {tuple(k.shape)}")
     if key_mask is not None:
@@ -869,7 +874,7 @@ def cross_attention(q, k, v, n_heads, key_mask=None, scale=None):
         if not (_rows_view(k, C, Tk, kvbs) and _rows_view(v, C, Tk, kvbs)) or kvbs < C * Tk:
             k, v, kvbs = k.contiguous(), v.contiguous(), C * Tk
         out = torch.empty((B, C, Tq), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.lib().amp_cross_attention(_ptr(q), int(qbs), _ptr(k), _ptr(v), int(kvbs), _ptr(key_mask), B, H, dk, Tq, Tk, scale, _ptr(out),
+        _lib.check(getattr(_lib.lib(), entry)(_ptr(q), int(qbs), _ptr(k), _ptr(v), int(kvbs), _ptr(key_mask), B, H, dk, Tq, Tk, scale, _ptr(out),
                                                   _stream(q)))
     return out
 
@@ -1065,3 +1070,144 @@ def embed_pos(tokens, weight, pe, pos0, alpha, x_scale=1.0, check=True):
         if check:
             _lib.check(_lib.lib().amp_embed_sum_check(_ptr(flag), _stream(y)))
     return y
+
+
+# ---- AudioLDM text-to-audio (csrc/conv2d_f16x3.hip, csrc/tta.hip; csrc/llama_nar.hip: amp_cross_attention at dk 32 / 64 / 128) ----------------
+def group_norm_stats(x, eps):
+    """GroupNorm(32) statistics of x [B, C, *] -> mean | rstd [B, 32, 2] (``amp_group_norm_stats``); C a multiple of 32"""
+    x = _lib.require_device_tensor(x, "group_norm_stats input")
+    if x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"group_norm_stats: expected a non-empty [B, C, ...] input, got {tuple(x.shape)}")
+    B, C = x.shape[:2]
+    mr = torch.empty((B, 32, 2), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_group_norm_stats(_ptr(x), B, C, x.numel() // (B * C), float(eps), _ptr(mr), _stream(x)))
+    return mr
+
+
+def group_norm(x, gamma, beta, eps, silu=False, stats=None):
+    """GroupNorm(32) of x [B, C, *] with an optional SiLU (``amp_group_norm_stats`` + ``amp_group_norm``); ``stats`` [B, 32, 2] if the caller
+    has them already"""
+    x = _lib.require_device_tensor(x, "group_norm input")
+    B, C = x.shape[:2]
+    _f32_dev(gamma, "gamma", "group_norm")
+    _f32_dev(beta, "beta", "group_norm")
+    if gamma.numel() != C or beta.numel() != C or gamma.device != x.device or beta.device != x.device:
+        raise ValueError(f"group_norm: gamma and beta must hold {C} values on {x.device}")
+    mr = group_norm_stats(x, eps) if stats is None else stats
+    y = torch.empty_like(x)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.lib().amp_group_norm(_ptr(x), _ptr(mr), _ptr(gamma.contiguous()), _ptr(beta.contiguous()), B, C, x.numel() // (B * C), int(bool(silu)),
+                                             _ptr(y), _stream(x)))
+    return y
+
+
+def geglu(u):
+    """u [B, 2F, T], the output of one stacked value | gate GEMM -> u[:, :F] * gelu(u[:, F:]) [B, F, T] (``amp_geglu``)"""
+    u = _lib.require_device_tensor(u, "geglu input")
+    if u.dim() != 3 or u.numel() == 0 or u.shape[1] % 2:
+        raise ValueError(f"geglu: expected a non-empty [B, 2F, T] input, got {tuple(u.shape)}")
+    B, F2, T = u.shape
+    y = torch.empty((B, F2 // 2, T), dtype=torch.float32, device=u.device)
+    with _lib.on_device(u.device):
+        _lib.check(_lib.lib().amp_geglu(_ptr(u), B, F2 // 2, T, _ptr(y), _stream(u)))
+    return y
+
+
+def cross_attention_hd(q, k, v, n_heads, key_mask=None, scale=None):
+    """``cross_attention`` at head dimension 32, 64 or 128 (``amp_cross_attention_hd``): the spatial transformer of AudioLDM"""
+    return _cross_attention("amp_cross_attention_hd", (32, 64, 128), q, k, v, n_heads, key_mask, scale)
+
+
+def conv2d_out_size(H, W, stride=1, up2=False):
+    return (2 * H, 2 * W) if up2 else ((H - 1) // stride + 1, (W - 1) // stride + 1)
+
+
+class Conv2d3x3:
+    """A 3 x 3 ``nn.Conv2d`` with padding 1 on the HIP path (``amp_conv2d_*``) over the parameters of the reference's module: weight
+    [Cout, Cin, 3, 3] and bias.  The packed device copy is rebuilt when a parameter, the device or the precision changes.  Under the "f32"
+    precision the same function runs as torch ops on the same device (not the hot path)."""
+
+    def __init__(self):
+        self._cache = HandleCache("amp_conv2d_destroy")
+
+    def _build(self, weight, bias, device):
+        w, b = host_f32(weight), host_f32(bias)
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or (b is not None and b.numel() != w.shape[0]):
+            raise ValueError(f"Conv2d3x3: expected a weight [Cout, Cin, 3, 3] and a bias [Cout], got {tuple(w.shape)}")
+        h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().amp_conv2d_create(w.shape[1], w.shape[0], _ptr(w), _ptr(b), ctypes.byref(h)))
+        return h
+
+    def handle(self, weight, bias, device):
+        sig = param_sig((weight, bias), str(device), _lib.get_precision())
+        c = self._cache
+        return c.handle if sig == c.sig else c.build(sig, self._build, weight, bias, device)
+
+    def plan(self, weight, bias, device, H, W, stride=1, up2=False):
+        """(K slices, row blocks a wave owns, channels of a K chunk) of this conv on an H x W map (``amp_conv2d_plan``): 1 slice is the single
+        launch with the epilogue on the accumulators.  A function of the conv and the map alone, never of the batch."""
+        ks, mi, kc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.lib().amp_conv2d_plan(self.handle(weight, bias, device), int(H), int(W), int(stride), int(bool(up2)), ctypes.byref(ks), ctypes.byref(mi),
+                                              ctypes.byref(kc)))
+        return ks.value, mi.value, kc.value
+
+    def __call__(self, x, weight, bias, stride=1, up2=False, norm=None, row_add=None, residual=None):
+        """x [B, Cin, H, W] -> [B, Cout, Ho, Wo].  norm = (mean_rstd [B, 32, 2], gamma [Cin], beta [Cin]): GroupNorm(32) + SiLU on load;
+        row_add [B, Cout] (or [B, Cout, 1, 1]; a column block of a wider [B, n] tensor is read in place); residual [B, Cout, Ho, Wo]."""
+        x = _lib.require_device_tensor(x, "conv2d input")
+        if x.dim() != 4 or x.numel() == 0 or x.shape[1] != weight.shape[1]:
+            raise ValueError(f"Conv2d3x3: expected a non-empty [B, {weight.shape[1]}, H, W] input, got {tuple(x.shape)}")
+        B, Cin, H, W = x.shape
+        Cout = weight.shape[0]
+        dev = x.device
+        stride, up2 = int(stride), bool(up2)
+        if stride not in (1, 2) or (up2 and stride != 1):
+            raise ValueError(f"Conv2d3x3: stride={stride} up2={up2} is not covered")
+        Ho, Wo = conv2d_out_size(H, W, stride, up2)
+        if row_add is not None:
+            _f32_dev(row_add, "row_add", "Conv2d3x3")
+            if row_add.dim() == 4 and tuple(row_add.shape[2:]) == (1, 1):
+                row_add = row_add[:, :, 0, 0]
+            if tuple(row_add.shape) != (B, Cout) or row_add.device != dev:
+                raise ValueError(f"Conv2d3x3: row_add must be {(B, Cout)} on {dev}, got {tuple(row_add.shape)}")
+            if (Cout > 1 and row_add.stride(1) != 1) or (B > 1 and row_add.stride(0) < Cout):
+                row_add = row_add.contiguous()
+        if residual is not None:
+            residual = _lib.require_device_tensor(residual, "conv2d residual")
+            if tuple(residual.shape) != (B, Cout, Ho, Wo) or residual.device != dev:
+                raise ValueError(f"Conv2d3x3: residual must be {(B, Cout, Ho, Wo)} on {dev}, got {tuple(residual.shape)}")
+        if norm is not None:
+            mr, gamma, beta = norm
+            for t, name, shape in ((mr, "mean_rstd", (B, 32, 2)), (gamma, "gamma", (Cin,)), (beta, "beta", (Cin,))):
+                _f32_dev(t, name, "Conv2d3x3")
+                if tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"Conv2d3x3: {name} must be a contiguous {shape} tensor on {dev}, got {tuple(t.shape)}")
+        if _lib.get_precision() == "f32":
+            a = x
+            if norm is not None:
+                g = Cin // 32
+                a = (x.reshape(B, 32, g, H * W) - mr[:, :, 0, None, None]) * mr[:, :, 1, None, None]
+                a = torch.nn.functional.silu(a.reshape(B, Cin, H, W) * gamma.detach()[None, :, None, None] + beta.detach()[None, :, None, None])
+            if up2:
+                a = torch.nn.functional.interpolate(a, scale_factor=2, mode="nearest")
+            y = torch.nn.functional.conv2d(a, weight.detach(), None if bias is None else bias.detach(), stride=stride, padding=1)
+            if row_add is not None:
+                y = y + row_add[:, :, None, None]
+            if residual is not None:
+                y = y + residual
+            return y
+        h = self.handle(weight, bias, dev)
+        y = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        with _lib.on_device(dev):
+            nbytes = L.amp_conv2d_workspace_bytes(h, B, H, W, stride, int(up2))
+            # the K slices' partial sums: a tensor of this call (the caching allocator hands the block back to later work of the same
+            # stream only), so no conv leaves memory held behind it
+            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev) if nbytes else None
+            mr, gamma, beta = norm if norm is not None else (None, None, None)
+            rbs = int(row_add.stride(0)) if row_add is not None and B > 1 else 0
+            _lib.check(L.amp_conv2d_forward(h, _ptr(x), B, H, W, stride, int(up2), _ptr(mr), _ptr(gamma), _ptr(beta), _ptr(row_add), rbs, _ptr(residual),
+                                            _ptr(y), _ptr(ws), nbytes, _stream(x)))
+        return y

@@ -109,7 +109,9 @@ typedef struct amp_gen amp_gen;
  * 157 (additive): amp_cross_attention (head dimension 64, no rotation, separate query and key lengths), amp_ns2_layer_* and amp_ns2_ode_step
  * (NaturalSpeech2 inference);
  * 158 (additive): amp_prefix_attention (causal without rotation at head dimension 64, with a run-time prefix), amp_pw_forward_vec_ln
- * (+ _workspace_bytes) and amp_embed_pos (VALL-E inference). */
+ * (+ _workspace_bytes) and amp_embed_pos (VALL-E inference);
+ * 159 (additive): amp_conv2d_* (3 x 3 Conv2d with stride, x2 up-sampling, GroupNorm + SiLU on load and a residual epilogue),
+ * amp_group_norm_stats, amp_group_norm, amp_geglu, and amp_cross_attention_hd: amp_cross_attention at head dimensions 32 and 128 beside 64 (AudioLDM). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -1183,6 +1185,64 @@ size_t amp_pw_forward_vec_ln_workspace_bytes(const amp_pw* h, int B);
  * AMP_ERR_UNSUPPORTED. */
 int amp_embed_pos(const long long* tokens_dev, const float* weight_dev, int rows, int D, const float* pe_dev, int pe_rows, int pos0, float x_scale,
                   const float* alpha_dev, int B, int T, float* y_dev, unsigned* flag_dev, void* stream);
+
+/* ---- AudioLDM text-to-audio (csrc/conv2d_f16x3.hip, csrc/tta.hip, csrc/llama_nar.hip; models/tta/ldm/audioldm.py, models/tta/ldm/attention.py,
+ * models/tta/autoencoder/autoencoder.py).  Channel-first fp32: a feature map [B, C, H, W] is the library's [B, C, T] with T = H*W and row
+ * pitch W, and the token sequence of the spatial transformer is the same tensor.  Every launch goes to the caller's stream; no allocation,
+ * no synchronisation, no workgroup waits for another; deterministic (fixed summation order, no atomics except the f16x3 range flag); an
+ * item's bits do not depend on what it is batched with. ---- */
+
+/* Conv2d 3 x 3 with zero padding 1 as a split-f16 implicit GEMM (K = 9 * Cin streamed through LDS per tap).
+ * amp_conv2d_create: weight [Cout, Cin, 3, 3] and bias [Cout] (NULL = zeros), host fp32.  Cin = 4 or a multiple of 32 up to 2048, Cout = 1, 4
+ * or a multiple of 32 up to 1024 (the odd ones are padded on the host); anything else AMP_ERR_UNSUPPORTED.  The kernel exists in the f16x3
+ * arithmetic only: under AMP_PRECISION_F32 create returns AMP_ERR_UNSUPPORTED and the drop-in modules run torch's conv (not the hot path).
+ * amp_conv2d_forward: x [B, Cin, H, W] -> y [B, Cout, Ho, Wo], any H, W >= 1 with H*W < 2^24, with the run-time options
+ *     stride 1 | 2       stride 2: Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1 (the UNet's Downsample)
+ *     up2                the conv reads the nearest-neighbour x2 up-sampling of x, source (y >> 1, x >> 1), Ho = 2H, Wo = 2W; the up-sampled
+ *                        tensor is never written; stride must be 1
+ *     mean_rstd_dev      [B, 32, 2] from amp_group_norm_stats with gamma_dev, beta_dev [Cin]: a staged element becomes
+ *                        silu((x - mean_g) * rstd_g * gamma_c + beta_c) before the split (Cin a multiple of 32); the padding stays exactly 0,
+ *                        as the reference pads the activated tensor.  NULL: x as it is (gamma / beta ignored)
+ *     epilogue           + bias[m], then + row_add_dev[b, m] (NULL = none; items row_add_batch_stride floats apart, 0 = dense: a column block
+ *                        of a wider [B, n] tensor is read in place), then + residual_dev[b, m, t] (NULL = none; y may not overlap it)
+ * Where B*Ho*Wo is small against the weights the K axis is cut into slices whose partial sums go to ws_dev (amp_conv2d_workspace_bytes, 0
+ * where no slice is needed; ws_dev may then be NULL) and a second launch adds them in slice order: the cut is a function of the handle and
+ * of Ho*Wo alone; amp_conv2d_plan states it for one feature map (the number of K slices, 1 = one launch with the epilogue on the accumulators;
+ * the row blocks a wave owns, 1 | 2; the channels of a K chunk, 32 | 64; any of the three pointers may be NULL).  Staged operands report to the op-level range flag (amp_range_check).
+ * AMP_ERR_INVALID with a message: a NULL handle / x / y, B, H or W < 1, B > 65535, mean_rstd without gamma / beta, a row_add stride below Cout, a workspace too small, y
+ * overlapping x or the residual, the workspace overlapping a tensor.  AMP_ERR_UNSUPPORTED: a stride other than 1 or 2, up2 with stride 2,
+ * H*W >= 2^24, B*Ho*Wo beyond 2^31, the norm with Cin = 4. */
+typedef struct amp_conv2d amp_conv2d;
+int amp_conv2d_create(int cin, int cout, const float* weight_host, const float* bias_host, amp_conv2d** out);
+int amp_conv2d_precision(const amp_conv2d* h);
+int amp_conv2d_plan(const amp_conv2d* h, int H, int W, int stride, int up2, int* k_slices, int* row_blocks_per_wave, int* chunk_channels);
+size_t amp_conv2d_workspace_bytes(const amp_conv2d* h, int B, int H, int W, int stride, int up2);
+int amp_conv2d_forward(const amp_conv2d* h, const float* x_dev, int B, int H, int W, int stride, int up2, const float* mean_rstd_dev,
+                       const float* gamma_dev, const float* beta_dev, const float* row_add_dev, long long row_add_batch_stride,
+                       const float* residual_dev, float* y_dev, void* ws_dev, size_t ws_bytes, void* stream);
+void amp_conv2d_destroy(amp_conv2d* h);
+
+/* GroupNorm(32) statistics of x [B, C, T]: mean_rstd [B, 32, 2] = mean | 1 / sqrt(var + eps) over each group's (C / 32) * T elements, biased
+ * variance as torch computes it.  Two passes, the second centred, summed in fp64 in an order fixed by the group's size: |mean| >> std costs
+ * nothing.  C a multiple of 32 (else AMP_ERR_UNSUPPORTED).  AMP_ERR_INVALID: a NULL pointer, B, C or T < 1, a negative or non-finite eps,
+ * mean_rstd overlapping x. */
+int amp_group_norm_stats(const float* x_dev, int B, int C, int T, float eps, float* mean_rstd_dev, void* stream);
+/* The apply: y = (x - mean_g) * rstd_g * gamma_c + beta_c, through SiLU when silu != 0; y may be x (element-wise in place) or must not overlap it.  For the places where no 3 x 3 conv
+ * follows the norm (SpatialTransformer.norm -> proj_in).  C a multiple of 32; C, B <= 65535. */
+int amp_group_norm(const float* x_dev, const float* mean_rstd_dev, const float* gamma_dev, const float* beta_dev, int B, int C, int T, int silu,
+                   float* y_dev, void* stream);
+
+/* amp_cross_attention at head dimension 32, 64 or 128: with num_heads = 8 the spatial transformer's head dimension is 32 / 64 / 128 at the UNet's
+ * three levels.  It serves attn1 (q | k | v row blocks of one stacked GEMM output, Tq = Tk = H*W) and attn2 (Tq = H*W against the text tokens).
+ * Everything amp_cross_attention states holds, with "dk other than 32, 64 or 128" as the refused head dimensions; at dk = 64 the two entries
+ * launch the same kernel and return the same bits.  dk = 32 is a new instantiation of the template; dk = 128 is amp_mh_attention's
+ * instantiation with its dynamic-LDS plan and the extents apart.  amp_cross_attention itself keeps refusing 32 and 128. */
+int amp_cross_attention_hd(const float* q_dev, long long q_batch_stride, const float* k_dev, const float* v_dev, long long kv_batch_stride,
+                           const unsigned char* key_mask_dev, int B, int H, int dk, int Tq, int Tk, float scale, float* out_dev, void* stream);
+
+/* GEGLU (attention.py:95-96) on the output u [B, 2F, T] of one stacked GEMM: y[b, f, t] = u[b, f, t] * gelu(u[b, F + f, t]), the first half the
+ * value and the second the gate, exact-erf GELU; y [B, F, T] dense, not overlapping u.  amp_swiglu's contract otherwise. */
+int amp_geglu(const float* u_dev, int B, int F, int T, float* y_dev, void* stream);
 
 #ifdef __cplusplus
 }
