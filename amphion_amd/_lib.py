@@ -266,6 +266,10 @@ _SIGNATURES = {
     "amp_pair_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_resblock_forward": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "amp_set_resblock_fusion": (c_int, [c_int]),
+    "amp_set_rb_guards": (c_int, [c_int]),
+    "amp_set_rb_split_plan": (c_int, [c_int, POINTER(c_int)]),
+    "amp_rb_launch_plan": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "amp_resblock_forward_ex": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "amp_conv_destroy": (None, [c_void_p]),
     "amp_set_small_conv": (c_int, [c_int]),
     "amp_set_conv_blk": (c_int, [c_int]),

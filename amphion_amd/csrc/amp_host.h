@@ -85,11 +85,13 @@ int default_precision();
 
 // ---- launch-policy switches: ONE configuration, read from the environment once (first use) and changed afterwards only
 // through the amp_set_* entry points the tests use for their bitwise A/B comparisons.  Nothing on a launch path calls getenv.
-// Environment forms exist for the FOUR switches a deployment may want without code (round 5 dropped AMP_FUSE_PAIRS, AMP_PAIR_STRIP,
+// Environment forms exist for the switches a deployment may want without code (round 5 dropped AMP_FUSE_PAIRS, AMP_PAIR_STRIP,
 // AMP_CONV_BLK, AMP_RB_SUM_FRAMES, AMP_RB_HORIZONTAL, AMP_RB_HORIZONTAL_FRAMES and AMP_GROUP_MB: amp_set_* or nothing):
 //   AMP_PRECISION     f32 | f16x3       arithmetic of the conv contractions (amp_set_precision), read in default_precision()
 //   AMP_RB_FUSION     0 .. 3            whole-ResBlock kernel: off | policy (default) | wherever built | + four-wave tiles
 //   AMP_AMPB_FUSION   0 .. 3            whole-AMPBlock kernel (BigVGAN): off | policy (default) | wherever built | + four-wave tiles
+//   AMP_RB_GUARDS     -1 .. 1           real x in the whole-ResBlock kernel's guard columns: policy (default) | never | always
+//   AMP_RB_SPLIT_PLAN a[,b[,c]]         pairs per launch of a three-pair resblock, forced ("3", "2,1", "1,2", "1,1,1"); unset: the plan
 //   AMP_RB_STREAMS    -1 .. 1           a stage's resblocks on concurrent streams: small launches only (default) | never | always
 // (+ AMP_LAUNCH_MANIFEST=<file>, the profiling manifest of runtime.hip, and AMP_GRAPH_CACHE=0 on the Python side.)
 // The policies these steer are in conv_host.hip (generator.hip for group_bytes / rb_streams); the amp_set_* entry points in runtime.hip.
@@ -100,6 +102,8 @@ struct Config {
     int pair_strips = -1;      // -1 policy, 0 per-tile kernel, 1 four-wave strips
     int strip_fit = -1;        // fitted strips of the fused-pair strip kernel: -1 the plan (strip_geometry, conv_host.hip), 0 never, 1 every strip launch
     int rb_fusion = 1;
+    int rb_guards = -1;        // RbArgs::gx: -1 the policy (conv_host.hip rb_geometry), 0 never, 1 wherever the first conv's reach fits the guard
+    int rb_plan[3] = {0, 0, 0};   // forced pairs per launch of a three-pair resblock (amp_set_rb_split_plan); {0, 0, 0}: rb_plan()'s cost model
     int ampb_fusion = 1;
     int conv_blk = kConvBlkDefault;
     size_t group_bytes = 0;
@@ -206,7 +210,22 @@ bool pair_tile_args(const amp_conv* c1, const amp_conv* c2, const float* x, int 
                     const int* lens, int len_mul, PairArgs* out);
 
 bool rb_supported(const amp_conv* const* c1, const amp_conv* const* c2, int np, int B, int T);
-int rb_split(const amp_conv* const* c1, int np, int B, int T);
+// geometry of one whole-resblock launch and the launches of a resblock (conv_host.hip rb_geometry / rb_plan)
+struct RbGeom {
+    int W;             // columns per tile, 0: the form does not cover these pairs
+    int rh0, rh;       // columns a tile loses either side with zero guards / in this launch (gx: less the first conv's reach)
+    int gx;            // RbArgs::gx
+    int NT0, NT;       // W - 2 * rh0, W - 2 * rh: output columns per tile
+    int tiles0, tiles; // ceil(T / NT0), ceil(T / NT)
+};
+struct RbPlan {
+    int n;                           // launches
+    int count[AMP_RB_MAX_PAIRS];     // pairs in each
+};
+RbGeom rb_geometry(int C, int k, const int* dil, int first, int count, int T, int form);
+RbPlan rb_plan(int C, int k, const int* dil, int np, int B, int T, bool ragged);
+RbPlan rb_plan(const amp_conv* const* c1, int np, int B, int T, bool ragged);
+int rb_form_of(int C, int k);
 // pairs [first, first + count) of the resblock's np (count < 0: all from `first`): x -> y
 int rb_run(const amp_conv* const* c1, const amp_conv* const* c2, int np, const float* x, int B, int T, float slope, float* y, int mode,
            float div, hipStream_t stream, const int* lens = nullptr, int len_mul = 1, int first = 0, int count = -1);

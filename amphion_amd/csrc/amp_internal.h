@@ -124,7 +124,8 @@ struct RbArgs {
     float sc1[AMP_RB_MAX_PAIRS], isc1[AMP_RB_MAX_PAIRS], sc2[AMP_RB_MAX_PAIRS], isc2[AMP_RB_MAX_PAIRS];   // 16 * 2^s and reciprocal
     int dil[AMP_RB_MAX_PAIRS];
     int np;                    // pairs in the block (1 .. AMP_RB_MAX_PAIRS)
-    int rh;                    // one-sided receptive field of the block: sum_p (k-1)/2 * (dil[p] + 1) columns
+    int rh;                    // columns a tile loses either side: sum_p (k-1)/2 * (dil[p] + 1), less the first conv's reach with gx
+    int gx;                    // 1: the guard columns hold the real staged x for the launch's first conv (its reach must fit them), 0: zeros
     int B, C, T;
     int tiles_per_item;        // ceil(T / (W - 2 * rh))
     int rev;                   // 1: descending tile order, see ConvArgs::rev

@@ -532,23 +532,68 @@ static int rb_form(int C, int k) {
 // the workgroups of a launch must at least fill the chip (256 CUs): a short single utterance keeps the pairs' 4x more numerous
 // tiles (same bits).  One utterance, forced either way (profiles/r3_lat_rb_threshold.txt): 3 s (134 tiles at stage 3) 1.07 ms on
 // pairs against 1.11-1.17 on this kernel; 10 s (451 tiles) 2.31 against 2.23.
+int rb_form_of(int C, int k) { return rb_form(C, k); }
 constexpr long long kRbMinWorkgroups = 256;
+// a tile's trip through HBM in units of one conv of its form, times C * k (rb_plan): fitted per form from the forced plans of
+// profiles/r8_rb_guards.txt, 160 - 295 (C = 64 k = 11: 253; k = 7: 196 - 294; C = 32 k = 11: 218 - 240; k = 7: 162 - 286; C = 64 k = 3: 206)
+constexpr double kRbTripMacs = 235.0;
 
+// guard columns either side of the LDS tile of form `form` (the RB_G of launch_rb's instantiations, rb_f16x3.hip)
+static int rb_guard_columns(int C, int form) { return (C == 128 || (C == 64 && form == 0)) ? 16 : 32; }
+
+// RbArgs::gx, real x in the guard columns for the launch's first conv: amp_set_rb_guards / AMP_RB_GUARDS -1 this policy, 0 never, 1 wherever
+// the first conv's reach fits the guard.  Same bits either way (tests/test_gpu_rb_guards.py).
+// policy (profiles/r8_rb_guards.txt: op level at B = 64, the benchmark's T, forms alternating in one process, ms per resblock, three rounds):
+//   C = 64 k = 11 (pairs 0-1 + pair 2) 3.256 - 3.272 -> 3.092 - 3.116 (19 + 19 -> 18 + 17 rounds of workgroups)
+//   C = 64 k = 7  whole 2.174 - 2.177 -> whole with guards 2.171 - 2.175 (still 19 rounds) -> pairs 0-1 + pair 2 2.135 - 2.137 (17 + 17)
+//   C = 32 k = 11 (eight waves) 1.786 - 1.803 -> 1.730 - 1.746 (19 -> 18 rounds)
+//   C = 32 k = 7  (four waves) 1.219 - 1.225 -> 1.217 - 1.219: inside the range, every split 5 - 15 % slower -- off
+//   k = 3: no round to save (RH 12 -> 11) and the staged guards are paid: C = 64 1.071 - 1.073 -> 1.079 - 1.081, C = 32 0.687 - 0.689 ->
+//   0.700 - 0.702 -- off.  k = 5 not measured: off.
+static bool rb_guards_wanted(int C, int k) {
+    const int m = cfg().rb_guards;
+    if (m >= 0) return m != 0;
+    return k >= 11 || (C == 64 && k >= 7);
+}
+
+// THE geometry of one launch of pairs [first, first + count) of a resblock (C channels, kernel k, dilations dil[]) in kernel form `form`:
+// rb_supported, rb_plan and rb_run take their numbers from here.  Every conv is evaluated on all W columns of the tile and a tile loses
+// rh0 = sum_p (k-1)/2 * (dil[p] + 1) columns either side -- less the first conv's reach (k-1)/2 * dil[first] where the guards hold real x
+// (gx): that conv's inputs left and right of the tile are then there.  A reach wider than the guard keeps rh0 and zero guards.
+RbGeom rb_geometry(int C, int k, const int* dil, int first, int count, int T, int form) {
+    RbGeom g{};
+    int max_dil = 1;
+    for (int p = first; p < first + count; ++p) {
+        max_dil = dil[p] > max_dil ? dil[p] : max_dil;
+        g.rh0 += (k - 1) / 2 * (dil[p] + 1);
+    }
+    g.W = form < 0 ? 0 : rb_tile(k, C, max_dil, form);
+    g.rh = g.rh0;
+    const int reach = (k - 1) / 2 * dil[first];
+    if (g.W > 0 && rb_guards_wanted(C, k) && reach <= rb_guard_columns(C, form)) { g.gx = 1; g.rh -= reach; }
+    g.NT = g.W - 2 * g.rh;
+    g.NT0 = g.W - 2 * g.rh0;
+    if (g.W > 0 && g.NT > 0) g.tiles = (T + g.NT - 1) / g.NT;
+    if (g.W > 0 && g.NT0 > 0) g.tiles0 = (T + g.NT0 - 1) / g.NT0;
+    return g;
+}
+static RbGeom rb_geometry(const amp_conv* const* c1, int first, int count, int T) {
+    int dil[AMP_RB_MAX_PAIRS] = {1, 1, 1};
+    for (int p = first; p < first + count && p < AMP_RB_MAX_PAIRS; ++p) dil[p] = c1[p]->dilation;
+    return rb_geometry(c1[0]->cin, c1[0]->k, dil, first, count, T, rb_form(c1[0]->cin, c1[0]->k));
+}
+
+// What the kernel covers and the grid floor are judged on the zero-guard geometry (NT0): the guards change how many tiles a launch has, not
+// which shapes run on it.
 bool rb_supported(const amp_conv* const* c1, const amp_conv* const* c2, int np, int B, int T) {
     if (np < 1 || np > AMP_RB_MAX_PAIRS) return false;
-    int max_dil = 1, rh = 0;
     for (int p = 0; p < np; ++p) {
         if (!c1[p] || !c2[p] || !pair_supported(c1[p], c2[p])) return false;
         if (c1[p]->cin != c1[0]->cin || c1[p]->k != c1[0]->k) return false;
-        max_dil = c1[p]->dilation > max_dil ? c1[p]->dilation : max_dil;
-        rh += (c1[p]->k - 1) / 2 * (c1[p]->dilation + 1);
     }
-    const int form = rb_form(c1[0]->cin, c1[0]->k);
-    if (form < 0) return false;
-    const int W = rb_tile(c1[0]->k, c1[0]->cin, max_dil, form);
-    if (W <= 0 || W - 2 * rh < W / 2) return false;          // at least half of every tile must be output
-    const int NT = W - 2 * rh;
-    if (rb_fusion_mode() == 1 && (long long)B * ((T + NT - 1) / NT) < kRbMinWorkgroups) return false;
+    const RbGeom g = rb_geometry(c1, 0, np, T);
+    if (g.W <= 0 || g.NT0 < g.W / 2) return false;          // at least half of every tile must be output
+    if (rb_fusion_mode() == 1 && (long long)B * g.tiles0 < kRbMinWorkgroups) return false;
     return true;
 }
 
@@ -557,19 +602,59 @@ bool rb_supported(const amp_conv* const* c1, const amp_conv* const* c2, int np, 
 // more trip of x through HBM.  Under the package power cap removed MFMAs convert to time in full: B = 64 3.45 -> 3.19 ms,
 // B = 32 1.68 -> 1.58, B = 16 0.89 -> 0.78; B = 8 (672 workgroups) 0.431 -> 0.443, hence the 1 024-workgroup floor; k = 7 (86 % kept) and
 // C = 32 k = 11 (88 %) are 1-4 % slower split (profiles/r5_l_rb_split.txt).  Same bits: what leaves a launch is the fp32 x the next pair
-// would have read from registers.  Returns the number of pairs in the first launch, 0 = one launch.
-int rb_split(const amp_conv* const* c1, int np, int B, int T) {
-    if (np != 3 || rb_fusion_mode() != 1) return 0;
-    int max_dil = 1, rh = 0;
-    for (int p = 0; p < np; ++p) {
-        max_dil = c1[p]->dilation > max_dil ? c1[p]->dilation : max_dil;
-        rh += (c1[p]->k - 1) / 2 * (c1[p]->dilation + 1);
+// would have read from registers.
+//
+// Round 8: the split is a PLAN, pairs per launch, chosen by one cost model in the manner of strip_geometry(): a launch of n convs takes
+// ceil(workgroups / slots) rounds of workgroups, and a round costs its n convs plus the trip of the tile through HBM, which in units of one
+// conv of the form is kRbTripConvs(C, k) = kRbTripMacs / (C * k) (a conv's time goes with C * C * k * W per tile, the trip's with C * W):
+//     cost = sum over launches of rounds * (convs + kRbTripMacs / (C * k))
+// With real x in the guards every launch sheds its own first conv's reach, so cutting before a wide conv buys columns: C = 64, k = 7 now
+// runs as {2, 1} (17 + 17 rounds instead of 19), C = 64, k = 11 stays {2, 1} ({1, 1, 1} measured 1.5 % slower, as the model has it).
+// Candidates: {3}, {2, 1}, {1, 2} and, with 2 048+ workgroups, {1, 1, 1}; never fewer launches than the round-5 rule above gives (that rule
+// was measured on MFMA counts down to 1 024 workgroups, where whole rounds say little); a tie keeps the round-5 plan; ragged batches and
+// launches under 1 024 workgroups keep it too.  amp_set_rb_split_plan / AMP_RB_SPLIT_PLAN force a plan in every fusion mode.
+RbPlan rb_plan(int C, int k, const int* dil, int np, int B, int T, bool ragged) {
+    RbPlan best{1, {np, 0, 0}};
+    if (np != 3) return best;
+    const int* f = cfg().rb_plan;
+    if (f[0] > 0) {
+        RbPlan forced{0, {0, 0, 0}};
+        for (int i = 0; i < 3 && f[i] > 0; ++i) forced.count[forced.n++] = f[i];
+        return forced;
     }
-    const int W = rb_tile(c1[0]->k, c1[0]->cin, max_dil, rb_form(c1[0]->cin, c1[0]->k));
-    const int NT = W - 2 * rh;
-    if (W <= 0 || 5 * NT >= 4 * W) return 0;
-    if ((long long)B * ((T + NT - 1) / NT) < 1024) return 0;
-    return 2;
+    if (rb_fusion_mode() != 1) return best;
+    const int form = rb_form(C, k);
+    const RbGeom whole = rb_geometry(C, k, dil, 0, np, T, form);
+    if (whole.W <= 0 || whole.NT0 <= 0) return best;
+    const long long wg0 = (long long)B * whole.tiles0;
+    if (wg0 < 1024) return best;
+    if (5 * whole.NT0 < 4 * whole.W) best = RbPlan{2, {2, 1, 0}};
+    if (ragged || !rb_guards_wanted(C, k)) return best;     // zero guards: the round-5 rule as it was measured
+    const long long slots = 256 * (form == 0 ? 2 : 1);
+    const double trip = kRbTripMacs / ((double)C * k);
+    auto cost = [&](const RbPlan& pl) {
+        double c = 0.0;
+        for (int l = 0, first = 0; l < pl.n; first += pl.count[l++]) {
+            const RbGeom g = rb_geometry(C, k, dil, first, pl.count[l], T, form);
+            if (g.W <= 0 || g.NT <= 0) return -1.0;
+            c += (double)(((long long)B * g.tiles + slots - 1) / slots) * (2.0 * pl.count[l] + trip);
+        }
+        return c;
+    };
+    double best_cost = cost(best);
+    const RbPlan cands[] = {{1, {3, 0, 0}}, {2, {2, 1, 0}}, {2, {1, 2, 0}}, {3, {1, 1, 1}}};
+    const int min_launches = best.n;
+    for (const RbPlan& pl : cands) {
+        if (pl.n < min_launches || (pl.n == 3 && wg0 < 2048)) continue;
+        const double c = cost(pl);
+        if (c >= 0.0 && (best_cost < 0.0 || c < best_cost)) { best_cost = c; best = pl; }
+    }
+    return best;
+}
+RbPlan rb_plan(const amp_conv* const* c1, int np, int B, int T, bool ragged) {
+    int dil[AMP_RB_MAX_PAIRS] = {1, 1, 1};
+    for (int p = 0; p < np && p < AMP_RB_MAX_PAIRS; ++p) dil[p] = c1[p]->dilation;
+    return rb_plan(c1[0]->cin, c1[0]->k, dil, np, B, T, ragged);
 }
 
 int rb_run(const amp_conv* const* c1, const amp_conv* const* c2, int np, const float* x, int B, int T, float slope, float* y, int mode,
@@ -579,30 +664,27 @@ int rb_run(const amp_conv* const* c1, const amp_conv* const* c2, int np, const f
     RbArgs a{};
     a.x = x; a.y = y;
     a.np = count < 0 ? np - first : count;
+    const RbGeom g = rb_geometry(c1, first, a.np, T);
+    if (g.W <= 0 || g.NT <= 0) { set_error("rb_run: pairs [%d, %d) have no whole-resblock tile", first, first + a.np); return AMP_ERR_UNSUPPORTED; }
     c1 += first;
     c2 += first;
-    int max_dil = 1;
     for (int p = 0; p < a.np; ++p) {
         a.wp1[p] = c1[p]->wp_dev; a.bias1[p] = c1[p]->bias_dev; a.wp2[p] = c2[p]->wp_dev; a.bias2[p] = c2[p]->bias_dev;
         a.sc1[p] = 16.f * c1[p]->wscale; a.isc1[p] = 1.f / a.sc1[p];
         a.sc2[p] = 16.f * c2[p]->wscale; a.isc2[p] = 1.f / a.sc2[p];
         a.dil[p] = c1[p]->dilation;
-        a.rh += (c1[p]->k - 1) / 2 * (c1[p]->dilation + 1);
-        max_dil = c1[p]->dilation > max_dil ? c1[p]->dilation : max_dil;
     }
     for (int p = a.np; p < AMP_RB_MAX_PAIRS; ++p) {   // never dereferenced; keep the pointers valid all the same
         a.wp1[p] = a.wp1[0]; a.bias1[p] = a.bias1[0]; a.wp2[p] = a.wp2[0]; a.bias2[p] = a.bias2[0]; a.dil[p] = 1;
     }
     a.B = B; a.C = c1[0]->cin; a.T = T;
-    const int form = rb_form(a.C, c1[0]->k);
-    const int W = rb_tile(c1[0]->k, a.C, max_dil, form);
-    const int NT = W - 2 * a.rh;
-    a.tiles_per_item = (T + NT - 1) / NT;
+    a.rh = g.rh; a.gx = g.gx;
+    a.tiles_per_item = g.tiles;
     a.slope = slope; a.mode = mode; a.div = div;
     a.lens = lens; a.len_mul = len_mul;
     a.range_flag = range_flag_for_current_device();
     a.rev = next_rev(lens);
-    AMP_HIP(launch_rb(c1[0]->k, a, form, stream));
+    AMP_HIP(launch_rb(c1[0]->k, a, rb_form(a.C, c1[0]->k), stream));
     return AMP_OK;
 }
 
@@ -871,6 +953,32 @@ int amp_resblock_forward(const amp_conv* const* c1, const amp_conv* const* c2, i
         return AMP_ERR_UNSUPPORTED;
     }
     return rb_run(c1, c2, n_pairs, x_dev, B, T, slope, y_dev, 0, 1.f, (hipStream_t)stream);
+}
+
+int amp_resblock_forward_ex(const amp_conv* const* c1, const amp_conv* const* c2, int n_pairs, const float* x_dev, int B, int T, float slope,
+                            float* y_dev, int mode, float div, float* tmp_dev, void* stream) {
+    if (!c1 || !c2 || !x_dev || !y_dev) { set_error("amp_resblock_forward_ex: null argument"); return AMP_ERR_INVALID; }
+    if (B <= 0 || T <= 0 || n_pairs < 1 || n_pairs > AMP_RB_MAX_PAIRS || mode < 0 || mode > 2) {
+        set_error("amp_resblock_forward_ex: B=%d T=%d n_pairs=%d mode=%d", B, T, n_pairs, mode);
+        return AMP_ERR_INVALID;
+    }
+    for (int p = 0; p < n_pairs; ++p) if (!c1[p] || !c2[p]) { set_error("amp_resblock_forward_ex: null conv handle"); return AMP_ERR_INVALID; }
+    if (!rb_supported(c1, c2, n_pairs, B, T)) {
+        set_error("amp_resblock_forward_ex: block (C=%d k=%d, %d pairs, B=%d T=%d) is not covered by the whole-resblock kernel under the "
+                  "current amp_set_resblock_fusion mode", c1[0]->cin, c1[0]->k, n_pairs, B, T);
+        return AMP_ERR_UNSUPPORTED;
+    }
+    const RbPlan pl = rb_plan(c1, n_pairs, B, T, false);
+    if (pl.n > 1 && !tmp_dev) { set_error("amp_resblock_forward_ex: a plan of %d launches needs tmp_dev", pl.n); return AMP_ERR_INVALID; }
+    const size_t be = (size_t)B * c1[0]->cin * T;
+    const float* cur = x_dev;
+    int first = 0;
+    for (int l = 0; l + 1 < pl.n; first += pl.count[l++]) {
+        float* dst = cur == tmp_dev ? tmp_dev + be : tmp_dev;
+        AMP_RC(rb_run(c1, c2, n_pairs, cur, B, T, slope, dst, 0, 1.f, (hipStream_t)stream, nullptr, 1, first, pl.count[l]));
+        cur = dst;
+    }
+    return rb_run(c1, c2, n_pairs, cur, B, T, slope, y_dev, mode, div, (hipStream_t)stream, nullptr, 1, first, -1);
 }
 
 int amp_ampblock_forward(const amp_conv* const* c1, const amp_conv* const* c2, int n_pairs, const float* alpha_dev,

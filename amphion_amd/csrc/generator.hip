@@ -631,7 +631,7 @@ static int wait_before_last(hipEvent_t wait, hipStream_t sj) {
     return AMP_OK;
 }
 
-// ResBlock1 (HiFi-GAN), U -> b.XS on sj with the MRF mode mode_last: the whole resblock in one or two launches, else pair by pair (a fused
+// ResBlock1 (HiFi-GAN), U -> b.XS on sj with the MRF mode mode_last: the whole resblock in one to three launches, else pair by pair (a fused
 // pair, or its two convs)
 static int run_resblock1(const Stage& s, const ResBlock& rb, const RbBufs& b, int mode_last, hipEvent_t wait, hipStream_t sj) {
     const int B = s.B, t = s.t;
@@ -639,11 +639,18 @@ static int run_resblock1(const Stage& s, const ResBlock& rb, const RbBufs& b, in
     const int nd = (int)rb.dil.size();
     RbPtrs q(rb);
     if (q.n && rb_supported(q.c1, q.c2, nd, B, t)) {
-        // the whole resblock in one launch: U -> XS (x and the residual never leave the CU in between) -- or in two, rb_split()
-        const int sp = rb_split(q.c1, nd, B, t);
-        if (sp > 0) AMP_RC(rb_run(q.c1, q.c2, nd, s.U, B, t, kLreluSlope, b.R, 0, 1.f, sj, s.lens, s.lm, 0, sp));
+        // the whole resblock in one launch: U -> XS (x and the residual never leave the CU in between) -- or in two
+        // or three: the launches of rb_plan(), x ping-ponging R <-> TMP in between as on the pair path below
+        const RbPlan pl = rb_plan(q.c1, nd, B, t, s.lens != nullptr);
+        const float* cur = s.U;
+        int first = 0;
+        for (int l = 0; l + 1 < pl.n; first += pl.count[l++]) {
+            float* dst = cur == b.R ? b.TMP : b.R;
+            AMP_RC(rb_run(q.c1, q.c2, nd, cur, B, t, kLreluSlope, dst, 0, 1.f, sj, s.lens, s.lm, first, pl.count[l]));
+            cur = dst;
+        }
         AMP_RC(wait_before_last(wait, sj));
-        return rb_run(q.c1, q.c2, nd, sp > 0 ? b.R : s.U, B, t, kLreluSlope, b.XS, mode_last, nk, sj, s.lens, s.lm, sp, -1);
+        return rb_run(q.c1, q.c2, nd, cur, B, t, kLreluSlope, b.XS, mode_last, nk, sj, s.lens, s.lm, first, -1);
     }
     const float* cur = s.U;
     for (int p = 0; p < nd; ++p) {

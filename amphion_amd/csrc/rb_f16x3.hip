@@ -19,7 +19,9 @@
 //               of pair_f16x3.hip's xt tile): each conv reads it (all waves), barrier, and its output -- leaky ReLU, the
 //               conv's zero padding outside the utterance, x16, hi/lo split, all in registers -- is written over it in
 //               place (every wave over its own columns), barrier.  The G guard columns either side are zero and are never
-//               written: they stand for the tile's unknown outside and keep every read in bounds.
+//               written: they stand for the tile's unknown outside and keep every read in bounds.  RbArgs::gx = 1: for the launch's
+//               FIRST conv they hold the real staged x instead (it is in HBM), that conv keeps all W columns, and they are zeroed in
+//               its seam -- RH shrinks by the first conv's reach (conv_host.hip rb_geometry).
 //   HBM         x is read once, y written once per resblock: 1/3 of the fused pairs' traffic, 1/15 of the unfused convs'.
 //
 // Per output element the operation order (bias, chunks, taps, the three MFMAs of a term, the fma of the residual, the MRF
@@ -80,10 +82,50 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
     if (O0 >= Tv) return;                     // tile beyond the utterance: unspecified by contract (workgroup-uniform)
     const int q0 = O0 - RH;                   // global column of tile column 0
 
-    // zero guards
-    for (int i = tid; i < NCH * 4 * 2 * RB_G; i += NTHR) {
-        const int row = i / (2 * RB_G), g = i - row * (2 * RB_G);
-        smem4[row * WL + (g < RB_G ? g : W + g)] = make_uint4(0u, 0u, 0u, 0u);
+    float range_max = 0.f;       // largest |staged operand| (x16 applied): beyond 65504 it left the f16 range (a.range_flag)
+    const float kpos = 16.f, kneg = 16.f * a.slope;
+    auto zero_guards = [&]() __attribute__((always_inline)) {
+        for (int i = tid; i < NCH * 4 * 2 * RB_G; i += NTHR) {
+            const int row = i / (2 * RB_G), g = i - row * (2 * RB_G);
+            smem4[row * WL + (g < RB_G ? g : W + g)] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+    // the same zeros in the first seam (gx), where the accumulators, the residual and the A ring leave no registers for a 16-B store and its
+    // index arithmetic: 4-B stores of ONE zero register at constant offsets from ONE address -- a thread keeps its guard column and word and
+    // walks the [chunk][plane][octet] rows
+    constexpr int ZRS = NTHR / (8 * RB_G);    // rows per sweep of the workgroup
+    static_assert(NTHR % (8 * RB_G) == 0 && (NCH * 4) % ZRS == 0, "the guard words of a row tile the workgroup");
+    auto rezero_guards = [&]() __attribute__((always_inline)) {
+        const int r = tid & (8 * RB_G - 1), g = r >> 2;
+        unsigned* pz = reinterpret_cast<unsigned*>(smem4) + ((tid / (8 * RB_G)) * WL + (g < RB_G ? g : W + g)) * 4 + (r & 3);
+#pragma unroll
+        for (int it = 0; it < NCH * 4 / ZRS; ++it) pz[it * ZRS * WL * 4] = 0u;
+    };
+    if (a.gx) {   // workgroup-uniform
+        // the guards of the launch's FIRST conv hold what lies there: lrelu(x) * 16, split, of global columns q0 - RB_G .. q0 - 1 and
+        // q0 + W .. q0 + W + RB_G - 1 (stage_x's text: the bits the neighbouring tile stages for the same element; zero outside
+        // [0, Tv) by select).  That conv's output is then valid on all W columns and the launch loses its reach less either side (a.rh,
+        // rb_geometry() in conv_host.hip).  One item = one 16-B unit: eight channels of both planes at one guard column.
+        const float* xg = a.x + (size_t)item * C * T;
+#pragma unroll 1
+        for (int i = tid; i < NCH * 2 * 2 * RB_G; i += NTHR) {
+            const int co = i / (2 * RB_G), g = i - co * (2 * RB_G);   // co = 2 * chunk + octet: channels 8 * co .. 8 * co + 7
+            const int lc = g < RB_G ? g : W + g;                      // LDS column
+            const int q = q0 - RB_G + lc;
+            const bool ok = (q >= 0) && (q < Tv);
+            const float* src = xg + (size_t)(8 * co) * T + (q < 0 ? 0 : (q < T ? q : T - 1));
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = src[(size_t)e * T];
+            struct { uint2 u; } fh0, fl0, fh1, fl1;
+            stage4_f16(ok ? v[0] : 0.f, ok ? v[1] : 0.f, ok ? v[2] : 0.f, ok ? v[3] : 0.f, kpos, kneg, range_max, fh0.u, fl0.u);
+            stage4_f16(ok ? v[4] : 0.f, ok ? v[5] : 0.f, ok ? v[6] : 0.f, ok ? v[7] : 0.f, kpos, kneg, range_max, fh1.u, fl1.u);
+            const int o4 = (co >> 1) * CHS + (co & 1) * WL + lc;
+            smem4[o4] = make_uint4(fh0.u.x, fh0.u.y, fh1.u.x, fh1.u.y);
+            smem4[o4 + 2 * WL] = make_uint4(fl0.u.x, fl0.u.y, fl1.u.x, fl1.u.y);
+        }
+    } else {
+        zero_guards();
     }
 
     // this lane's columns: tile column colw + 32 t, global column q0 + that
@@ -121,8 +163,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
     }
     AMP_PIN_VMEM();
 
-    float range_max = 0.f;       // largest |staged operand| (x16 applied): beyond 65504 it left the f16 range (a.range_flag)
-    const float kpos = 16.f, kneg = 16.f * a.slope;
     // x (registers) -> lrelu, the conv's zero padding, x16, hi / lo -> the LDS tile; what stage_store of pair_f16x3.hip does
     auto stage_x = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -202,6 +242,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void rb_f16x3_kernel(const RbArgs 
             // ---- c1: kernel KT, dilation d_p ----
             conv(a.wp1[p], a.bias1[p], a.sc1[p], a.dil[p], a.wp2[p]);
             __syncthreads();                      // every wave has read the tile
+            if (p == 0 && a.gx) rezero_guards();    // real x served the launch's first conv only: from here on the outside is unknown again
             {   // seam: xt = lrelu(c1(.)) -> the tile, in place (pair_f16x3.hip's seam)
                 const float i1 = a.isc1[p];
                 const float slope = a.slope;
@@ -275,7 +316,7 @@ static hipError_t launch_rb_one(const RbArgs& a, hipStream_t stream) {
     dim3 grid((unsigned)(a.B * a.tiles_per_item));
     note_kernel("rb_f16x3_kernel", KT, WM, WN, NI, RING, RB_G);
     note_work(grid.x, a.np * 2 * 2.0 * a.C * a.C * KT * (double)a.T * a.B / 1e9, 4.0 * a.B * (double)a.C * a.T * (2 + (a.mode ? 1 : 0)) / 1e6,
-              "whole ResBlock C=%d k=%d T=%d B=%d: %d convs%s", a.C, KT, a.T, a.B, 2 * a.np, a.mode ? " +sum" : "");
+              "whole ResBlock C=%d k=%d T=%d B=%d%s rh=%d: %d convs%s", a.C, KT, a.T, a.B, a.gx ? " guards=x" : "", a.rh, 2 * a.np, a.mode ? " +sum" : "");
     hipLaunchKernelGGL((rb_f16x3_kernel<KT, WM, WN, NI, RING, RB_G>), grid, dim3(64 * WM * WN), lds, stream, a);
     return hipGetLastError();
 }

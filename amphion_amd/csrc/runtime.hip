@@ -151,6 +151,15 @@ Config::Config() {
         return (v < lo || v > hi) ? dflt : v;
     };
     rb_fusion = num("AMP_RB_FUSION", 0, 3, 1);
+    rb_guards = num("AMP_RB_GUARDS", -1, 1, -1);
+    if (const char* e = getenv("AMP_RB_SPLIT_PLAN")) {   // "3" | "2,1" | "1,2" | "1,1,1"; anything else: the plan
+        int v[3] = {0, 0, 0};
+        const int n = sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]);
+        int sum = 0;
+        for (int i = 0; i < 3; ++i) sum += (i < n && v[i] > 0) ? v[i] : 0;
+        if (n >= 1 && sum == 3 && v[0] > 0 && (n < 2 || v[1] > 0) && (n < 3 || v[2] > 0))
+            for (int i = 0; i < 3; ++i) rb_plan[i] = i < n ? v[i] : 0;
+    }
     ampb_fusion = num("AMP_AMPB_FUSION", 0, 3, 1);
     rb_streams = num("AMP_RB_STREAMS", -1, 1, -1);
     // a deployment that still sets one of the switches round 5 removed must hear about it -- once, here (AMP_GROUP_MB bounded the
@@ -210,7 +219,9 @@ extern "C" {
 // amp_pw_forward_vec_ln, amp_embed_pos (valle.hip)
 // 159 (additive): AudioLDM text-to-audio -- amp_conv2d_* (conv2d_f16x3.hip), amp_group_norm_stats, amp_group_norm, amp_geglu (tta.hip) and
 // amp_cross_attention_hd: amp_cross_attention at head dimensions 32 and 128 beside 64 (llama_nar.hip)
-int amp_version(void) { return 159; }
+// 160 (additive): amp_set_rb_guards, amp_set_rb_split_plan, amp_rb_launch_plan and amp_resblock_forward_ex (real x in the whole-ResBlock
+// kernel's guard columns and the launch plan of a resblock, conv_host.hip rb_geometry / rb_plan)
+int amp_version(void) { return 160; }
 const char* amp_last_error(void) { return g_err; }
 
 int amp_set_precision(int precision) {
@@ -290,6 +301,40 @@ int amp_set_conv_blk(int mode) {
 int amp_set_resblock_fusion(int mode) {
     if (mode < -1 || mode > 3) { set_error("amp_set_resblock_fusion: mode=%d", mode); return AMP_ERR_INVALID; }
     cfg().rb_fusion = mode < 0 ? 1 : mode;
+    return AMP_OK;
+}
+
+int amp_set_rb_guards(int mode) {
+    if (mode < -1 || mode > 1) { set_error("amp_set_rb_guards: %d (-1 the policy, 0 never: zero guards, 1 wherever the first conv's reach fits)", mode); return AMP_ERR_INVALID; }
+    cfg().rb_guards = mode;
+    return AMP_OK;
+}
+
+int amp_set_rb_split_plan(int n, const int* counts) {
+    int v[3] = {0, 0, 0}, sum = 0;
+    if (n < 0 || n > 3 || (n > 0 && !counts)) { set_error("amp_set_rb_split_plan: n=%d (0 the plan, 1 .. 3 launches)", n); return AMP_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) { v[i] = counts[i]; sum += v[i]; if (v[i] < 1) sum = -99; }
+    if (n > 0 && sum != 3) { set_error("amp_set_rb_split_plan: the launches must hold 1+ pairs each and 3 together"); return AMP_ERR_INVALID; }
+    for (int i = 0; i < 3; ++i) cfg().rb_plan[i] = v[i];
+    return AMP_OK;
+}
+
+int amp_rb_launch_plan(int C, int k, const int* dilations, int n_pairs, int B, int T, int ragged, int* n_launches, int* pairs, int* gx,
+                       int* out_columns, int* tiles_per_item) {
+    if (B < 1 || T < 1 || n_pairs < 1 || n_pairs > AMP_RB_MAX_PAIRS || !dilations || !n_launches || !pairs || !gx || !out_columns || !tiles_per_item) {
+        set_error("amp_rb_launch_plan: B=%d T=%d n_pairs=%d or a null pointer", B, T, n_pairs);
+        return AMP_ERR_INVALID;
+    }
+    const int form = rb_form_of(C, k);
+    int dil[AMP_RB_MAX_PAIRS] = {1, 1, 1};
+    for (int p = 0; p < n_pairs; ++p) dil[p] = dilations[p];
+    const RbPlan pl = rb_plan(C, k, dil, n_pairs, B, T, ragged != 0);
+    *n_launches = pl.n;
+    for (int l = 0, first = 0; l < pl.n; first += pl.count[l++]) {
+        const RbGeom g = rb_geometry(C, k, dil, first, pl.count[l], T, form);
+        if (g.W <= 0 || g.NT <= 0) { set_error("amp_rb_launch_plan: no whole-resblock kernel for C=%d k=%d under the current fusion mode", C, k); return AMP_ERR_UNSUPPORTED; }
+        pairs[l] = pl.count[l]; gx[l] = g.gx; out_columns[l] = g.NT; tiles_per_item[l] = g.tiles;
+    }
     return AMP_OK;
 }
 

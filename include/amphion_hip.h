@@ -111,7 +111,8 @@ typedef struct amp_gen amp_gen;
  * 158 (additive): amp_prefix_attention (causal without rotation at head dimension 64, with a run-time prefix), amp_pw_forward_vec_ln
  * (+ _workspace_bytes) and amp_embed_pos (VALL-E inference);
  * 159 (additive): amp_conv2d_* (3 x 3 Conv2d with stride, x2 up-sampling, GroupNorm + SiLU on load and a residual epilogue),
- * amp_group_norm_stats, amp_group_norm, amp_geglu, and amp_cross_attention_hd: amp_cross_attention at head dimensions 32 and 128 beside 64 (AudioLDM). */
+ * amp_group_norm_stats, amp_group_norm, amp_geglu, and amp_cross_attention_hd: amp_cross_attention at head dimensions 32 and 128 beside 64 (AudioLDM);
+ * 160 (additive): amp_set_rb_guards, amp_set_rb_split_plan, amp_rb_launch_plan and amp_resblock_forward_ex (whole-resblock launches). */
 int amp_version(void);
 const char* amp_last_error(void);
 /* Number of HIP devices visible (0 when there is no GPU); never fails. */
@@ -417,6 +418,22 @@ int amp_resblock_forward(const amp_conv* const* c1, const amp_conv* const* c2, i
  * late stages when the launch fills the chip); 2: wherever the kernel is built, any grid; 3: as 2 with the four-wave
  * tiles (two workgroups per CU) at C = 32 (512 columns) and at C = 64, k <= 5 (256 columns).  Bit-identical results in every mode (tests/test_gpu_resblock.py); env AMP_RB_FUSION. */
 int amp_set_resblock_fusion(int mode);
+/* amp_version 160.  The whole-resblock kernel's tile has guard columns either side that stand for its unknown outside.  For the FIRST conv of a
+ * launch the outside is known (x is in memory): with the guards holding the real staged x that conv keeps all its columns and a tile loses
+ * (k-1)/2 * dilation fewer columns either side.  amp_set_rb_guards: -1 (default) the measured policy, 0 never, 1 wherever that reach fits the
+ * guard; env AMP_RB_GUARDS.  A three-pair resblock runs as one to three launches chosen by a cost model (rounds of workgroups x convs + the
+ * extra trip through memory); amp_set_rb_split_plan(n, counts) forces n launches of counts[i] pairs (sum 3), n = 0 gives the plan back; env
+ * AMP_RB_SPLIT_PLAN="2,1".  Bit-identical results under every setting (tests/test_gpu_rb_guards.py).
+ * amp_rb_launch_plan reports, without a device, the launches of a resblock (C, k, dilations) at (B, T) under the current switches: pairs,
+ * gx (guards hold x), output columns per tile and tiles per item of each (arrays of 3).
+ * amp_resblock_forward_ex is amp_resblock_forward walking that plan, with the MRF mode of the last launch (0: y = v, 1: y += v,
+ * 2: y = (y + v) / div); tmp_dev: 2 * B * C * T floats of scratch, needed when the plan has more than one launch. */
+int amp_set_rb_guards(int mode);
+int amp_set_rb_split_plan(int n, const int* counts);
+int amp_rb_launch_plan(int C, int k, const int* dilations, int n_pairs, int B, int T, int ragged, int* n_launches, int* pairs, int* gx,
+                       int* out_columns, int* tiles_per_item);
+int amp_resblock_forward_ex(const amp_conv* const* c1, const amp_conv* const* c2, int n_pairs, const float* x_dev, int B, int T, float slope,
+                            float* y_dev, int mode, float div, float* tmp_dev, void* stream);
 /* The n_kernels resblocks of a generator stage on CONCURRENT streams (they read the same stage tensor and only meet in the MRF mean,
  * hifigan.py:208-214 / bigvgan.py:320-327): -1 (default) while B * T <= 4096 mel frames -- small batches, whose launches do not
  * fill the chip and whose forward is a chain of ~50 dependent launches; 0 never; 1 always.  Only the launch of each resblock that
