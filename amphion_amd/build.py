@@ -46,7 +46,7 @@ def _units():
              ("tconv_f16x3.hip", "tconv_f16x3.o", []), ("semantic_prepare.hip", "semantic_prepare.o", []),
              ("seanet.hip", "seanet.o", []), ("lstm.hip", "lstm.o", []), ("evq.hip", "evq.o", []),
              ("dsconv_f16x3.hip", "dsconv_f16x3.o", []), ("llama_nar.hip", "llama_nar.o", []),
-             ("maskgct.hip", "maskgct.o", []), ("llama_ar.hip", "llama_ar.o", []), ("fastspeech.hip", "fastspeech.o", []),
+             ("maskgct.hip", "maskgct.o", []), ("llama_ar.hip", "llama_ar.o", []), ("pw_vec.hip", "pw_vec.o", []), ("fastspeech.hip", "fastspeech.o", []),
              ("ns2_layer_f16x3.hip", "ns2_layer_f16x3.o", []), ("ns2.hip", "ns2.o", []),
              ("valle.hip", "valle.o", []), ("conv2d_f16x3.hip", "conv2d_f16x3.o", []), ("tta.hip", "tta.o", [])]
     for kt in CONV_TAPS:

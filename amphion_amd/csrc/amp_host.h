@@ -20,6 +20,13 @@
 
 #define AMP_RC(expr) do { int rc__ = (expr); if (rc__ != AMP_OK) return rc__; } while (0)
 
+// do the byte ranges [p, p + pn) and [q, q + qn) share a byte?  An empty range overlaps nothing.
+inline bool ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const char* a = static_cast<const char*>(p);
+    const char* b = static_cast<const char*>(q);
+    return pn && qn && a < b + qn && b < a + pn;
+}
+
 // ---- amp_conv: one (transposed) convolution with packed weights on the device (conv_host.hip) -----------------------
 struct amp_conv {
     int transposed = 0, cin = 0, cout = 0, k = 0, stride = 1, dilation = 1, padding = 0;
@@ -41,7 +48,7 @@ struct amp_conv {
     }
 };
 
-// ---- amp_pw: one nn.Linear along the channel axis (pw_f16x3.hip; the T = 1 form of llama_ar.hip reads the same packed weights) ----------
+// ---- amp_pw: one nn.Linear along the channel axis (pw_f16x3.hip; the T = 1 form of pw_vec.hip reads the same packed weights) ----------
 struct amp_pw {
     int cin = 0, cout = 0;
     int precision = amp::PREC_F16X3;

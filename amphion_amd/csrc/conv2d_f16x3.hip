@@ -272,12 +272,6 @@ int c2_plan(const amp_conv2d* h, int B, int H, int W, int stride, int up2, C2Pla
     return AMP_OK;
 }
 
-bool c2_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const char* x = (const char*)a;
-    const char* y = (const char*)b;
-    return x < y + bn && y < x + an;
-}
-
 template <int KS, int MI>
 void c2_launch(bool norm, dim3 grid, hipStream_t stream, const Conv2dArgs& a) {
     if (norm) hipLaunchKernelGGL((conv2d_f16x3_kernel<KS, MI, true>), grid, dim3(256), 0, stream, a);
@@ -349,10 +343,10 @@ int amp_conv2d_forward(const amp_conv2d* h, const float* x_dev, int B, int H, in
     const size_t need = amp_conv2d_workspace_bytes(h, B, H, W, stride, up2);
     if (need && (!ws_dev || ws_bytes < need)) { set_error("amp_conv2d_forward: workspace of %zu bytes, %zu needed", ws_dev ? ws_bytes : (size_t)0, need); return AMP_ERR_INVALID; }
     const size_t xbytes = (size_t)B * h->cin * H * W * sizeof(float), ybytes = (size_t)B * h->cout * p.To * sizeof(float);
-    if (c2_overlap(x_dev, xbytes, y_dev, ybytes)) { set_error("amp_conv2d_forward: y overlaps x"); return AMP_ERR_INVALID; }
-    if (residual_dev && c2_overlap(residual_dev, ybytes, y_dev, ybytes)) { set_error("amp_conv2d_forward: y overlaps the residual"); return AMP_ERR_INVALID; }
-    if (need && (c2_overlap(ws_dev, need, y_dev, ybytes) || c2_overlap(ws_dev, need, x_dev, xbytes) ||
-                 (residual_dev && c2_overlap(ws_dev, need, residual_dev, ybytes)))) {
+    if (ranges_overlap(x_dev, xbytes, y_dev, ybytes)) { set_error("amp_conv2d_forward: y overlaps x"); return AMP_ERR_INVALID; }
+    if (residual_dev && ranges_overlap(residual_dev, ybytes, y_dev, ybytes)) { set_error("amp_conv2d_forward: y overlaps the residual"); return AMP_ERR_INVALID; }
+    if (need && (ranges_overlap(ws_dev, need, y_dev, ybytes) || ranges_overlap(ws_dev, need, x_dev, xbytes) ||
+                 (residual_dev && ranges_overlap(ws_dev, need, residual_dev, ybytes)))) {
         set_error("amp_conv2d_forward: the workspace overlaps a tensor");
         return AMP_ERR_INVALID;
     }

@@ -169,11 +169,6 @@ static int dw_pack(const std::vector<float>& W, int rows, int cols, std::vector<
     return pack_matrix_f16x3("amp_dw_finalize", rows, cols, rows / 32, (cols + 15) / 16, [&](int m, int i) { return W[(size_t)m * cols + i]; }, wp, inv_scale);
 }
 
-static bool dw_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char *pa = (const char*)a, *pb = (const char*)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 // shape checks shared by every entry that takes (B, L): refusals come before any launch
 static int dw_check_BL(const amp_dw* h, int B, long long L, const char* who) {
     if (!h) { set_error("%s: null handle", who); return AMP_ERR_INVALID; }
@@ -463,12 +458,12 @@ int amp_dw_layer(const amp_dw* h, int layer, const float* x_dev, const float* co
     if (layer < 0 || layer >= h->d.residual_layers) { set_error("amp_dw_layer: layer %d of %d", layer, h->d.residual_layers); return AMP_ERR_INVALID; }
     if (!x_dev || !cond_dev || !dconst_dev || !x_out_dev || !skip_out_dev || dconst_batch_stride < 0) { set_error("amp_dw_layer: bad argument"); return AMP_ERR_INVALID; }
     const size_t bytes = (size_t)B * h->d.residual_channels * L * sizeof(float);
-    if (dw_overlap(x_dev, bytes, x_out_dev, bytes)) {
+    if (ranges_overlap(x_dev, bytes, x_out_dev, bytes)) {
         set_error("amp_dw_layer: x_out must not overlap x (other tiles read x at +- the dilation): ping-pong two buffers");
         return AMP_ERR_INVALID;
     }
-    if (dw_overlap(skip_out_dev, bytes, x_dev, bytes) || dw_overlap(skip_out_dev, bytes, x_out_dev, bytes)) { set_error("amp_dw_layer: skip_out overlaps x or x_out"); return AMP_ERR_INVALID; }
-    if (skip_in_dev && skip_in_dev != skip_out_dev && dw_overlap(skip_in_dev, bytes, skip_out_dev, bytes)) { set_error("amp_dw_layer: skip_in must be skip_out or not overlap it"); return AMP_ERR_INVALID; }
+    if (ranges_overlap(skip_out_dev, bytes, x_dev, bytes) || ranges_overlap(skip_out_dev, bytes, x_out_dev, bytes)) { set_error("amp_dw_layer: skip_out overlaps x or x_out"); return AMP_ERR_INVALID; }
+    if (skip_in_dev && skip_in_dev != skip_out_dev && ranges_overlap(skip_in_dev, bytes, skip_out_dev, bytes)) { set_error("amp_dw_layer: skip_in must be skip_out or not overlap it"); return AMP_ERR_INVALID; }
     return dw_layer_run(h, layer, x_dev, cond_dev, dconst_dev, dconst_batch_stride, skip_in_dev, x_out_dev, skip_out_dev, B, L, (hipStream_t)stream_);
 }
 

@@ -1,9 +1,8 @@
 // The decoding side of Vevo's autoregressive transformer (models/vc/autoregressive_transformer/ar_model.py: a causal LlamaForCausalLM that
 // generates one token at a time).  The prefill is amp_rope_attention_causal (llama_nar.hip) over the pointwise GEMM; a decode step has one
-// column per item and is made of the launches of this file:
+// column per item and is made of the launches of this file and of its Linears (pw_vec.hip: amp_pw_forward_vec):
 //     amp_kv_append            rope(k) and v of T new columns into the per-layer caches [B, H dk, Lmax]
 //     amp_attention_decode     one query per (item, head) over cache columns [0, L): exact fp32, keys split across workgroups
-//     amp_pw_forward_vec       an amp_pw Linear at T = 1 (B <= 8) as a weight-streaming matrix-vector product, fp32 multiplies
 //     amp_ar_sample            HF's processor chain (repetition penalty, EOS suppression, temperature, top-k, top-p) and the draw
 // Plain fp32 on the vector pipe with accurate expf and correctly rounded divides.  Deterministic: every reduction runs in a fixed order, no
 // atomics on data (the sampler ORs bits of an LDS bitmap of the ids seen so far), no workgroup waits for another.
@@ -157,152 +156,6 @@ __global__ __launch_bounds__(DEC_S) void decode_combine_kernel(DecodeArgs a) {
         o = fmaf(e[2 + d], f, o);
     }
     a.out[(size_t)bh * dk + d] = o / l;
-}
-
-// ---- amp_pw_forward_vec ---------------------------------------------------------------------------------------------------------------
-// The handle's packed weights are MFMA A fragments: per 32-row block and K unit one 16-byte entry per lane (amp_host.h: pack_a_f16x3 --
-// a hi and a lo plane, lane l = row l & 31, channels 16 u + 8 (l >> 5) + 0 .. 7; conv_host.hip's exact-fp32 pack -- one plane of floats,
-// channels 8 u + 2 p + (l >> 5)).  Workgroup (mb, ks) of four waves streams the units [u0, u1) of row block mb, wave w the units
-// u0 + w, u0 + w + 4, ...: a wave's load of an entry is 1 KiB contiguous, every weight is read once, by one lane.  The weight is hi + lo
-// (exact in fp32: the two halves of one fp32 value) or the fp32 weight itself, the product an fp32 fma against the x of up to NB items,
-// staged once per workgroup in LDS (zeros beyond Cin and beyond B).  Lanes l and l ^ 32 share a row: one exchange, then the four waves in
-// order through LDS, and the slice's partial sums go to the workspace [ks][b][row].  pw_vec_epilogue_kernel adds the K slices in ascending
-// order and applies scale, bias and the residual epilogue.  The K slices give every Linear of the recipe more workgroups than CUs
-// (pw_vec_ksplit); no atomics, the order of every sum is fixed by the shape alone.
-constexpr int PV_XS = 1024;      // channels of x a workgroup stages per item
-constexpr int PV_MAXB = 8;
-
-struct PwVecArgs {
-    const void* wp;
-    const float* x;       // [B, Cin], items xbs apart
-    long long xbs;
-    float* ws;            // [ksplit][B][rows_pad]
-    int Cin, B, units, per_slice, rows_pad;
-};
-
-template <int F32, int NB>
-__global__ __launch_bounds__(256) void pw_vec_kernel(PwVecArgs a) {
-    constexpr int CU = F32 ? 8 : 16;                       // channels per unit
-    __shared__ __attribute__((aligned(16))) float xs[NB][PV_XS];
-    __shared__ float red[4][NB][32];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hi = lane >> 5;
-    const int mb = blockIdx.x, ks = blockIdx.y;
-    const int u0 = ks * a.per_slice;
-    const int u1 = u0 + a.per_slice < a.units ? u0 + a.per_slice : a.units;
-    const int nch = (u1 - u0) * CU;                        // <= PV_XS (host)
-    for (int idx = tid; idx < NB * nch; idx += 256) {
-        const int b = idx / nch, cl = idx - b * nch, ch = u0 * CU + cl;
-        xs[b][cl] = (b < a.B && ch < a.Cin) ? a.x[(size_t)b * (size_t)a.xbs + ch] : 0.f;
-    }
-    __syncthreads();
-    float acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
-    if (F32) {
-        const float4* wp = reinterpret_cast<const float4*>(a.wp) + (size_t)mb * a.units * 64 + lane;
-#pragma unroll 4
-        for (int u = u0 + w; u < u1; u += 4) {
-            const float4 wv = wp[(size_t)u * 64];
-            const int xo = (u - u0) * 8 + hi;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                acc[b] = fmaf(wv.x, xs[b][xo], acc[b]);
-                acc[b] = fmaf(wv.y, xs[b][xo + 2], acc[b]);
-                acc[b] = fmaf(wv.z, xs[b][xo + 4], acc[b]);
-                acc[b] = fmaf(wv.w, xs[b][xo + 6], acc[b]);
-            }
-        }
-    } else {
-        const uint4* wp = reinterpret_cast<const uint4*>(a.wp) + (size_t)mb * a.units * 128 + lane;
-#pragma unroll 4
-        for (int u = u0 + w; u < u1; u += 4) {
-            union { uint4 q; _Float16 h[8]; } vh, vl;
-            vh.q = wp[(size_t)u * 128];
-            vl.q = wp[(size_t)u * 128 + 64];
-            float wv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) wv[e] = (float)vh.h[e] + (float)vl.h[e];
-            const int xo = (u - u0) * 16 + 8 * hi;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const float4 x0 = *reinterpret_cast<const float4*>(&xs[b][xo]), x1 = *reinterpret_cast<const float4*>(&xs[b][xo + 4]);
-                acc[b] = fmaf(wv[0], x0.x, acc[b]);
-                acc[b] = fmaf(wv[1], x0.y, acc[b]);
-                acc[b] = fmaf(wv[2], x0.z, acc[b]);
-                acc[b] = fmaf(wv[3], x0.w, acc[b]);
-                acc[b] = fmaf(wv[4], x1.x, acc[b]);
-                acc[b] = fmaf(wv[5], x1.y, acc[b]);
-                acc[b] = fmaf(wv[6], x1.z, acc[b]);
-                acc[b] = fmaf(wv[7], x1.w, acc[b]);
-            }
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const float t = acc[b] + __shfl_xor(acc[b], 32);
-        if (hi == 0) red[w][b][lane] = t;
-    }
-    __syncthreads();
-    if (tid < NB * 32) {
-        const int b = tid >> 5, r = tid & 31;
-        if (b < a.B) a.ws[((size_t)ks * a.B + b) * a.rows_pad + mb * 32 + r] = ((red[0][b][r] + red[1][b][r]) + red[2][b][r]) + red[3][b][r];
-    }
-}
-
-__global__ __launch_bounds__(256) void pw_vec_epilogue_kernel(const float* __restrict__ ws, int ksplit, int B, int rows_pad, int Cout, float scale,
-                                                              const float* __restrict__ bias, const float* __restrict__ gamma, const float* res,
-                                                              float* y) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= B * Cout) return;
-    const int b = idx / Cout, row = idx - b * Cout;
-    float s = 0.f;
-    for (int ks = 0; ks < ksplit; ++ks) s += ws[((size_t)ks * B + b) * rows_pad + row];
-    float v = s * scale + bias[row];
-    if (res) v = res[idx] + gamma[row] * v;
-    y[idx] = v;
-}
-
-// K slices: enough that the staged x fits (PV_XS channels) and that the grid has at least 256 workgroups, at least one unit per wave
-static int pw_vec_ksplit(int units, int cu, int row_blocks) {
-    const int fit = (units * cu + PV_XS - 1) / PV_XS;
-    int want = (256 + row_blocks - 1) / row_blocks;
-    const int most = units / 4 > 1 ? units / 4 : 1;
-    if (want > most) want = most;
-    return want > fit ? want : fit;
-}
-
-struct PwVecPlan {
-    int f32, units, cu, row_blocks, ksplit, per_slice;
-    const void* wp;
-    const float* bias;
-    float scale;
-};
-
-static int pw_vec_plan(const amp_pw* p, PwVecPlan* out) {
-    PwVecPlan pl{};
-    pl.f32 = p->precision == PREC_F32;
-    pl.row_blocks = (p->cout + 31) / 32;
-    if (pl.f32) {
-        if (!p->conv || p->conv->KT != 1 || p->conv->precision != PREC_F32) { set_error("amp_pw_forward_vec: the handle's exact-fp32 conv is not a one-tap pack"); return AMP_ERR_UNSUPPORTED; }
-        pl.units = p->conv->nchunks; pl.cu = KC;
-        pl.wp = p->conv->wp_dev; pl.bias = p->conv->bias_dev; pl.scale = 1.f;
-    } else {
-        pl.units = p->nsteps * 4; pl.cu = KC16;
-        pl.wp = p->wp_dev; pl.bias = p->bias_dev; pl.scale = 16.f * p->inv_scale;     // 1 / 2^s: the staged x carries no x16 here
-    }
-    pl.ksplit = pw_vec_ksplit(pl.units, pl.cu, pl.row_blocks);
-    pl.per_slice = (pl.units + pl.ksplit - 1) / pl.ksplit;
-    pl.ksplit = (pl.units + pl.per_slice - 1) / pl.per_slice;                          // no empty slice
-    *out = pl;
-    return AMP_OK;
-}
-
-template <int F32>
-static void pw_vec_launch(const PwVecArgs& a, int nb, dim3 grid, hipStream_t st) {
-    if (nb <= 1) hipLaunchKernelGGL((pw_vec_kernel<F32, 1>), grid, dim3(256), 0, st, a);
-    else if (nb <= 2) hipLaunchKernelGGL((pw_vec_kernel<F32, 2>), grid, dim3(256), 0, st, a);
-    else if (nb <= 4) hipLaunchKernelGGL((pw_vec_kernel<F32, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((pw_vec_kernel<F32, 8>), grid, dim3(256), 0, st, a);
 }
 
 // ---- amp_ar_sample --------------------------------------------------------------------------------------------------------------------
@@ -476,12 +329,6 @@ __global__ __launch_bounds__(AS_THREADS) void ar_sample_kernel(ArSampleArgs a) {
     }
 }
 
-static bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
-    const char* a = reinterpret_cast<const char*>(p);
-    const char* b = reinterpret_cast<const char*>(q);
-    return pn && qn && a < b + qn && b < a + pn;
-}
-
 }  // namespace amp
 
 using namespace amp;
@@ -501,8 +348,8 @@ int amp_kv_append(const float* k_dev, const float* v_dev, long long batch_stride
     if (batch_stride < (long long)H * dk * T) { set_error("amp_kv_append: batch stride %lld < H*dk*T", batch_stride); return AMP_ERR_INVALID; }
     const size_t span = ((size_t)(B - 1) * (size_t)batch_stride + (size_t)H * dk * T) * sizeof(float);
     const size_t cbytes = (size_t)B * H * dk * Lmax * sizeof(float);
-    if (overlaps(kcache_dev, cbytes, vcache_dev, cbytes) || overlaps(kcache_dev, cbytes, k_dev, span) || overlaps(kcache_dev, cbytes, v_dev, span) ||
-        overlaps(vcache_dev, cbytes, k_dev, span) || overlaps(vcache_dev, cbytes, v_dev, span)) {
+    if (ranges_overlap(kcache_dev, cbytes, vcache_dev, cbytes) || ranges_overlap(kcache_dev, cbytes, k_dev, span) || ranges_overlap(kcache_dev, cbytes, v_dev, span) ||
+        ranges_overlap(vcache_dev, cbytes, k_dev, span) || ranges_overlap(vcache_dev, cbytes, v_dev, span)) {
         set_error("amp_kv_append: the caches must not overlap each other or k / v");
         return AMP_ERR_INVALID;
     }
@@ -546,9 +393,9 @@ int amp_attention_decode(const float* q_dev, long long q_batch_stride, const flo
     }
     const size_t qspan = ((size_t)(B - 1) * (size_t)q_batch_stride + (size_t)H * dk) * sizeof(float);
     const size_t obytes = (size_t)B * H * dk * sizeof(float), cbytes = (size_t)B * H * dk * Lmax * sizeof(float);
-    if (overlaps(out_dev, obytes, q_dev, qspan) || overlaps(out_dev, obytes, kcache_dev, cbytes) || overlaps(out_dev, obytes, vcache_dev, cbytes) ||
-        overlaps(workspace_dev, need, q_dev, qspan) || overlaps(workspace_dev, need, kcache_dev, cbytes) ||
-        overlaps(workspace_dev, need, vcache_dev, cbytes) || overlaps(workspace_dev, need, out_dev, obytes)) {
+    if (ranges_overlap(out_dev, obytes, q_dev, qspan) || ranges_overlap(out_dev, obytes, kcache_dev, cbytes) || ranges_overlap(out_dev, obytes, vcache_dev, cbytes) ||
+        ranges_overlap(workspace_dev, need, q_dev, qspan) || ranges_overlap(workspace_dev, need, kcache_dev, cbytes) ||
+        ranges_overlap(workspace_dev, need, vcache_dev, cbytes) || ranges_overlap(workspace_dev, need, out_dev, obytes)) {
         set_error("amp_attention_decode: out and the workspace must not overlap q, the caches or each other");
         return AMP_ERR_INVALID;
     }
@@ -574,60 +421,6 @@ int amp_attention_decode(const float* q_dev, long long q_batch_stride, const flo
     return AMP_OK;
 }
 
-size_t amp_pw_forward_vec_workspace_bytes(const amp_pw* p, int B) {
-    PwVecPlan pl;
-    if (!p || B < 1 || B > PV_MAXB || pw_vec_plan(p, &pl) != AMP_OK) return 0;
-    return (size_t)pl.ksplit * B * (size_t)(pl.row_blocks * 32) * sizeof(float);
-}
-
-int amp_pw_forward_vec(const amp_pw* p, const float* x_dev, long long x_batch_stride, int B, int epilogue, const float* gamma_dev,
-                       const float* res_dev, float* y_dev, float* workspace_dev, size_t workspace_bytes, void* stream) {
-    if (!p || !x_dev || !y_dev || !workspace_dev) { set_error("amp_pw_forward_vec: null argument"); return AMP_ERR_INVALID; }
-    if (B < 1 || B > PV_MAXB) { set_error("amp_pw_forward_vec: B=%d is outside [1, %d]", B, PV_MAXB); return AMP_ERR_INVALID; }
-    if (epilogue != AMP_PW_BIAS && epilogue != AMP_PW_SCALE_RES) {
-        set_error("amp_pw_forward_vec: epilogue %d (AMP_PW_BIAS or AMP_PW_SCALE_RES)", epilogue);
-        return AMP_ERR_INVALID;
-    }
-    if (epilogue == AMP_PW_SCALE_RES && (!gamma_dev || !res_dev)) { set_error("amp_pw_forward_vec: AMP_PW_SCALE_RES needs gamma and res"); return AMP_ERR_INVALID; }
-    if (x_batch_stride == 0) x_batch_stride = p->cin;
-    if (x_batch_stride < p->cin) { set_error("amp_pw_forward_vec: batch stride %lld < cin", x_batch_stride); return AMP_ERR_INVALID; }
-    PwVecPlan pl;
-    AMP_RC(pw_vec_plan(p, &pl));
-    const int rows_pad = pl.row_blocks * 32;
-    const size_t need = (size_t)pl.ksplit * B * (size_t)rows_pad * sizeof(float);
-    if (workspace_bytes < need) {
-        set_error("amp_pw_forward_vec: workspace of %zu bytes, %zu needed (amp_pw_forward_vec_workspace_bytes)", workspace_bytes, need);
-        return AMP_ERR_INVALID;
-    }
-    const size_t xspan = ((size_t)(B - 1) * (size_t)x_batch_stride + (size_t)p->cin) * sizeof(float), ybytes = (size_t)B * p->cout * sizeof(float);
-    if (overlaps(y_dev, ybytes, x_dev, xspan) || overlaps(workspace_dev, need, x_dev, xspan) || overlaps(workspace_dev, need, y_dev, ybytes)) {
-        set_error("amp_pw_forward_vec: x, y and the workspace must not overlap");
-        return AMP_ERR_INVALID;
-    }
-    if (epilogue == AMP_PW_SCALE_RES && res_dev != y_dev && overlaps(res_dev, ybytes, y_dev, ybytes)) {
-        set_error("amp_pw_forward_vec: res must be y or not overlap it");
-        return AMP_ERR_INVALID;
-    }
-    PwVecArgs a{};
-    a.wp = pl.wp; a.x = x_dev; a.xbs = x_batch_stride; a.ws = workspace_dev;
-    a.Cin = p->cin; a.B = B; a.units = pl.units; a.per_slice = pl.per_slice; a.rows_pad = rows_pad;
-    const dim3 grid((unsigned)pl.row_blocks, (unsigned)pl.ksplit);
-    hipStream_t st = (hipStream_t)stream;
-    note_kernel("pw_vec_kernel", pl.f32, B);
-    note_work((unsigned long long)grid.x * grid.y, 2.0 * (double)p->cout * p->cin * B / 1e9, 4.0 * (double)rows_pad * pl.units * pl.cu / 1e6,
-              "pw vec %d->%d epi=%d B=%d grid=%ux%u", p->cin, p->cout, epilogue, B, grid.x, grid.y);
-    if (pl.f32) pw_vec_launch<1>(a, B, grid, st);
-    else pw_vec_launch<0>(a, B, grid, st);
-    AMP_HIP(hipGetLastError());
-    const unsigned nb = (unsigned)((B * p->cout + 255) / 256);
-    note_kernel("pw_vec_epilogue_kernel");
-    note_work(nb, 0.0, 4.0 * (double)B * p->cout * (pl.ksplit + 2) / 1e6, "pw vec epilogue C=%d B=%d slices=%d", p->cout, B, pl.ksplit);
-    hipLaunchKernelGGL(pw_vec_epilogue_kernel, dim3(nb), dim3(256), 0, st, workspace_dev, pl.ksplit, B, rows_pad, p->cout, pl.scale, pl.bias,
-                       epilogue == AMP_PW_SCALE_RES ? gamma_dev : nullptr, epilogue == AMP_PW_SCALE_RES ? res_dev : nullptr, y_dev);
-    AMP_HIP(hipGetLastError());
-    return AMP_OK;
-}
-
 int amp_ar_sample(const float* logits_dev, long long batch_stride, int B, int V, const float* q_dev, long long* ids_dev, long long ids_capacity,
                   int n_ids, int eos_id, int suppress_eos, float temperature, int top_k, double top_p, float repetition_penalty, void* stream) {
     if (!logits_dev || !q_dev || !ids_dev) { set_error("amp_ar_sample: null argument"); return AMP_ERR_INVALID; }
@@ -646,7 +439,7 @@ int amp_ar_sample(const float* logits_dev, long long batch_stride, int B, int V,
     if (batch_stride < V) { set_error("amp_ar_sample: batch stride %lld < V", batch_stride); return AMP_ERR_INVALID; }
     const size_t lbytes = ((size_t)(B - 1) * (size_t)batch_stride + (size_t)V) * sizeof(float), qbytes = (size_t)B * V * sizeof(float);
     const size_t ibytes = (size_t)B * (size_t)ids_capacity * sizeof(long long);
-    if (overlaps(ids_dev, ibytes, logits_dev, lbytes) || overlaps(ids_dev, ibytes, q_dev, qbytes)) {
+    if (ranges_overlap(ids_dev, ibytes, logits_dev, lbytes) || ranges_overlap(ids_dev, ibytes, q_dev, qbytes)) {
         set_error("amp_ar_sample: ids must not overlap logits / q");
         return AMP_ERR_INVALID;
     }

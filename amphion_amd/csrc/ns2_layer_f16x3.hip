@@ -226,12 +226,6 @@ struct amp_ns2_layer {
     }
 };
 
-static bool ns2_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const char* x = (const char*)a;
-    const char* y = (const char*)b;
-    return x < y + bn && y < x + an;
-}
-
 extern "C" {
 
 int amp_ns2_layer_create(int hidden, int dilation, const float* conv_weight_host, const float* conv_bias_host, const float* out_weight_host,
@@ -296,17 +290,17 @@ int amp_ns2_layer_forward(const amp_ns2_layer* h, const float* x_dev, const floa
     }
     const size_t n = (size_t)B * H * T, bytes = n * sizeof(float);
     const size_t wsn = amp_ns2_layer_workspace_bytes(h, B, T);
-    if (x_out_dev != x_dev && ns2_overlap(x_out_dev, bytes, x_dev, bytes)) { set_error("amp_ns2_layer_forward: x_out must be x or not overlap it"); return AMP_ERR_INVALID; }
-    if (ns2_overlap(skip_out_dev, bytes, x_dev, bytes) || ns2_overlap(skip_out_dev, bytes, x_out_dev, bytes)) {
+    if (x_out_dev != x_dev && ranges_overlap(x_out_dev, bytes, x_dev, bytes)) { set_error("amp_ns2_layer_forward: x_out must be x or not overlap it"); return AMP_ERR_INVALID; }
+    if (ranges_overlap(skip_out_dev, bytes, x_dev, bytes) || ranges_overlap(skip_out_dev, bytes, x_out_dev, bytes)) {
         set_error("amp_ns2_layer_forward: skip_out overlaps x or x_out");
         return AMP_ERR_INVALID;
     }
-    if (skip_in_dev && skip_in_dev != skip_out_dev && ns2_overlap(skip_in_dev, bytes, skip_out_dev, bytes)) {
+    if (skip_in_dev && skip_in_dev != skip_out_dev && ranges_overlap(skip_in_dev, bytes, skip_out_dev, bytes)) {
         set_error("amp_ns2_layer_forward: skip_in must be skip_out or not overlap it");
         return AMP_ERR_INVALID;
     }
     for (const void* p : {(const void*)x_dev, (const void*)x_out_dev, (const void*)skip_out_dev, (const void*)skip_in_dev})
-        if (p && ns2_overlap(ws_dev, wsn, p, bytes)) { set_error("amp_ns2_layer_forward: the workspace overlaps a tensor"); return AMP_ERR_INVALID; }
+        if (p && ranges_overlap(ws_dev, wsn, p, bytes)) { set_error("amp_ns2_layer_forward: the workspace overlaps a tensor"); return AMP_ERR_INVALID; }
     hipStream_t stream = (hipStream_t)stream_;
     float* ws = (float*)ws_dev;
     const dim3 egrid((unsigned)((T + 255) / 256), (unsigned)H, (unsigned)B);

@@ -92,12 +92,6 @@ __global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ u,
 
 using namespace amp;
 
-static bool tta_overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const char* x = (const char*)a;
-    const char* y = (const char*)b;
-    return x < y + bn && y < x + an;
-}
-
 extern "C" {
 
 int amp_group_norm_stats(const float* x_dev, int B, int C, int T, float eps, float* mean_rstd_dev, void* stream) {
@@ -108,7 +102,7 @@ int amp_group_norm_stats(const float* x_dev, int B, int C, int T, float eps, flo
     if (C % GN_GROUPS) { set_error("amp_group_norm_stats: C=%d is not a multiple of 32", C); return AMP_ERR_UNSUPPORTED; }
     if ((long long)B * GN_GROUPS > 0x7fffffffll) { set_error("amp_group_norm_stats: B=%d is beyond the grid", B); return AMP_ERR_UNSUPPORTED; }
     const size_t n = (size_t)(C / GN_GROUPS) * T;
-    if (tta_overlap(x_dev, (size_t)B * C * T * sizeof(float), mean_rstd_dev, (size_t)B * GN_GROUPS * 2 * sizeof(float))) {
+    if (ranges_overlap(x_dev, (size_t)B * C * T * sizeof(float), mean_rstd_dev, (size_t)B * GN_GROUPS * 2 * sizeof(float))) {
         set_error("amp_group_norm_stats: mean_rstd overlaps x");
         return AMP_ERR_INVALID;
     }
@@ -128,7 +122,7 @@ int amp_group_norm(const float* x_dev, const float* mean_rstd_dev, const float* 
     if (C % GN_GROUPS) { set_error("amp_group_norm: C=%d is not a multiple of 32", C); return AMP_ERR_UNSUPPORTED; }
     if (C > 65535 || B > 65535) { set_error("amp_group_norm: C=%d or B=%d is beyond the grid (65535)", C, B); return AMP_ERR_UNSUPPORTED; }
     const size_t bytes = (size_t)B * C * T * sizeof(float);
-    if (y_dev != x_dev && tta_overlap(x_dev, bytes, y_dev, bytes)) { set_error("amp_group_norm: y must be x or not overlap it"); return AMP_ERR_INVALID; }
+    if (y_dev != x_dev && ranges_overlap(x_dev, bytes, y_dev, bytes)) { set_error("amp_group_norm: y must be x or not overlap it"); return AMP_ERR_INVALID; }
     const dim3 grid((unsigned)((T + 255) / 256), (unsigned)C, (unsigned)B);
     note_kernel("group_norm_apply_kernel");
     note_work((unsigned long long)grid.x * grid.y * grid.z, 0.0, 8.0 * (double)B * C * T / 1e6, "group norm apply C=%d T=%d B=%d silu=%d", C, T, B, silu ? 1 : 0);
@@ -140,7 +134,7 @@ int amp_group_norm(const float* x_dev, const float* mean_rstd_dev, const float* 
 int amp_geglu(const float* u_dev, int B, int F, int T, float* y_dev, void* stream) {
     if (!u_dev || !y_dev || B < 1 || F < 1 || T < 1 || B > 65535) { set_error("amp_geglu: bad argument (B=%d F=%d T=%d)", B, F, T); return AMP_ERR_INVALID; }
     const size_t n = (size_t)F * T;
-    if (tta_overlap(u_dev, 2 * (size_t)B * n * sizeof(float), y_dev, (size_t)B * n * sizeof(float))) { set_error("amp_geglu: y must not overlap u"); return AMP_ERR_INVALID; }
+    if (ranges_overlap(u_dev, 2 * (size_t)B * n * sizeof(float), y_dev, (size_t)B * n * sizeof(float))) { set_error("amp_geglu: y must not overlap u"); return AMP_ERR_INVALID; }
     const int vec = (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_dev) | reinterpret_cast<uintptr_t>(y_dev)) & 15) == 0 ? 1 : 0;
     const size_t threads = vec ? n >> 2 : n;
     const size_t blocks = (threads + 255) / 256;

@@ -432,10 +432,7 @@ def silu(x, out=None):
     x = _lib.require_device_tensor(x, "silu input")
     if x.numel() == 0:
         raise ValueError(f"silu: empty input {tuple(x.shape)}")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"silu: out must be a contiguous float32 {tuple(x.shape)} on {x.device}")
+    out = _out_like("silu", out, x)
     with _lib.on_device(x.device):
         _lib.check(_lib.lib().amp_silu(_ptr(x), x.numel(), _ptr(out), _stream(x)))
     return out
@@ -466,11 +463,10 @@ def rms_norm_c_adaptive(x, w, eps=1e-6):
         w = w[:, :, 0]
     if w.dim() != 2 or tuple(w.shape) != (B, C):
         raise ValueError(f"rms_norm_c_adaptive: expected a weight of shape {(B, C)}, got {tuple(w.shape)}")
-    if (C > 1 and w.stride(1) != 1) or (B > 1 and w.stride(0) < C):
-        w = w.contiguous()
+    w, wbs = _rows_2d(w, C)
     y = torch.empty_like(x)
     with _lib.on_device(x.device):
-        _lib.check(_lib.lib().amp_rms_norm_c_adaptive(_ptr(x), _ptr(w), int(w.stride(0)) if B > 1 else C, B, C, T, float(eps), _ptr(y), _stream(x)))
+        _lib.check(_lib.lib().amp_rms_norm_c_adaptive(_ptr(x), _ptr(w), wbs, B, C, T, float(eps), _ptr(y), _stream(x)))
     return y
 
 
@@ -496,6 +492,89 @@ def _rows_view(t, C, T, bstride):
     return t.stride(2) == 1 and (C == 1 or t.stride(1) == T) and (t.shape[0] == 1 or t.stride(0) == bstride)
 
 
+def _row_blocks(tensors, C, T):
+    """``tensors`` [B, C, T] as a kernel with ONE batch stride for all of them reads them -> (tensors, batch stride): in place when every one
+    is contiguous or a row block of a wider tensor (``_rows_view``) at one batch stride >= C * T, else contiguous copies of all of them"""
+    t0 = tensors[0]
+    bstride = t0.stride(0) if t0.shape[0] > 1 else max(t0.stride(0), C * T)
+    if bstride >= C * T:
+        for t in tensors:
+            if not _rows_view(t, C, T, bstride):
+                break
+        else:
+            return tensors, bstride
+    return [t.contiguous() for t in tensors], C * T
+
+
+def _rows_2d(t, C):
+    """``t`` [B, C], one row per item, as a kernel reads it -> (t, batch stride): in place when the rows are contiguous and at least C apart
+    (a slice of a wider tensor), else a contiguous copy.  The stride of a single row is C"""
+    B = t.shape[0]
+    if (C > 1 and t.stride(1) != 1) or (B > 1 and t.stride(0) < C):
+        t = t.contiguous()
+    return t, int(t.stride(0)) if B > 1 else C
+
+
+def _f32_dev(t, name, who):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
+    return t
+
+
+def _key_mask_u8(who, key_mask, B, Tk, device):
+    """a key mask [B, Tk] (nonzero = valid) as the contiguous bytes the attention kernels read; None stays None"""
+    if key_mask is None:
+        return None
+    if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, Tk) or key_mask.device != device:
+        raise ValueError(f"{who}: key_mask must be a {(B, Tk)} tensor on {device}")
+    if key_mask.dtype != torch.uint8:
+        key_mask = (key_mask != 0).to(torch.uint8)
+    return key_mask.contiguous()
+
+
+def _heads(who, C, n_heads, dks):
+    """(H, dk) of C channels in ``n_heads`` heads, for a kernel that covers the head dimensions ``dks``"""
+    H = int(n_heads)
+    if H < 1 or C % H:
+        raise ValueError(f"{who}: {C} channels do not divide into {H} heads")
+    dk = C // H
+    if dk not in dks:
+        raise ValueError(f"{who}: head dimension {dk} is not covered (dk = {' / '.join(map(str, dks))})")
+    return H, dk
+
+
+def _sdpa_cf(q, k, v, H, mask, scale):
+    """the exact-fp32 route of the attention functions: ``scaled_dot_product_attention`` on channel-first q [B, H*dk, Tq] and k, v
+    [B, H*dk, Tk] under the boolean ``mask`` (broadcastable to [B, H, Tq, Tk], True = visible, or None) -> [B, H*dk, Tq].  q and k may come
+    with their heads split already, as [B, H, T, dk] (``rope_attention`` rotates them in that form)"""
+    B, C, Tq = v.shape[0], v.shape[1], q.shape[-1] if q.dim() == 3 else q.shape[2]
+    qq, kk, vv = (t if t.dim() == 4 else t.reshape(B, H, C // H, t.shape[2]).transpose(2, 3) for t in (q, k, v))
+    o = torch.nn.functional.scaled_dot_product_attention(qq, kk, vv, attn_mask=mask, scale=scale)
+    return o.transpose(2, 3).reshape(B, C, Tq).contiguous()
+
+
+def _out_like(who, out, x):
+    """the ``out`` argument of an element-wise op on x: a new tensor, or the caller's contiguous float32 tensor of x's shape on x's device"""
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float32 {tuple(x.shape)} on {x.device}")
+    return out
+
+
+def _vec_input(who, x):
+    """the [B, cin, 1] column of the T = 1 Linears -> (x, B, cin, batch stride): read in place when it is a row block of a wider tensor"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        _f32_dev(x, "x", who)
+    if x.dim() != 3 or x.shape[2] != 1 or x.numel() == 0:
+        raise ValueError(f"{who}: expected a [B, cin, 1] input, got {tuple(x.shape)}")
+    B, cin = x.shape[0], x.shape[1]
+    # _rows_2d's rule, spelled out: every Linear of a decode step comes through here, and the step is bound by host work per launch
+    if (cin > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < cin):
+        x = x.contiguous()
+    return x, B, cin, int(x.stride(0)) if B > 1 else cin
+
+
 def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None, causal=False):
     """Non-causal multi-head self-attention with rotary position embedding (HF's rotate-half form) and a KEY mask (``amp_rope_attention``).
 
@@ -511,27 +590,17 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None, causal
         raise ValueError(f"rope_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
                          f"{tuple(v.shape)}")
     B, C, T = q.shape
-    H = int(n_heads)
-    if H < 1 or C % H:
-        raise ValueError(f"rope_attention: {C} channels do not divide into {H} heads")
-    dk = C // H
-    if dk not in (64, 96):
-        raise ValueError(f"rope_attention: head dimension {dk} is not covered (dk = 64 or 96)")
+    H, dk = _heads("rope_attention", C, n_heads, (64, 96))
     if B < 1 or T < 1:
         raise ValueError(f"rope_attention: empty input {tuple(q.shape)}")
     if tuple(cos.shape) != (T, dk // 2) or tuple(sin.shape) != (T, dk // 2) or cos.device != q.device or sin.device != q.device:
         raise ValueError(f"rope_attention: cos and sin must be {(T, dk // 2)} on {q.device}, got {tuple(cos.shape)} and {tuple(sin.shape)}")
     cos, sin = cos.contiguous(), sin.contiguous()
-    if key_mask is not None:
-        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
-            raise ValueError(f"rope_attention: key_mask must be a {(B, T)} tensor on {q.device}")
-        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
-            key_mask = (key_mask != 0).to(torch.uint8)
-        key_mask = key_mask.contiguous()
+    key_mask = _key_mask_u8("rope_attention", key_mask, B, T, q.device)
     scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
     with _lib.on_device(q.device):
         if _lib.get_precision() == "f32":
-            def rope(x):
+            def rope(x):                                     # -> [B, H, T, dk], contiguous
                 x = x.reshape(B, H, dk, T).transpose(2, 3)
                 c, s = torch.cat((cos, cos), -1), torch.cat((sin, sin), -1)
                 return x * c + torch.cat((-x[..., dk // 2:], x[..., : dk // 2]), -1) * s
@@ -539,12 +608,8 @@ def rope_attention(q, k, v, n_heads, cos, sin, key_mask=None, scale=None, causal
             if causal:
                 tri = torch.ones((T, T), dtype=torch.bool, device=q.device).tril()[None, None]
                 m = tri if m is None else m & tri
-            o = torch.nn.functional.scaled_dot_product_attention(rope(q), rope(k), v.reshape(B, H, dk, T).transpose(2, 3), attn_mask=m, scale=scale)
-            return o.transpose(2, 3).reshape(B, C, T).contiguous()
-        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
-        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            bstride = C * T
+            return _sdpa_cf(rope(q), rope(k), v, H, m, scale)
+        (q, k, v), bstride = _row_blocks((q, k, v), C, T)
         out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
         entry = _lib.lib().amp_rope_attention_causal if causal else _lib.lib().amp_rope_attention
         _lib.check(entry(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), _ptr(key_mask), B, H, dk, T, scale, _ptr(out), _stream(q)))
@@ -568,10 +633,7 @@ def mask_sample(logits, k, u=None, temperature=1.0):
     k = int(k)
     if not 2 <= V <= 8192 or not 1 <= k <= V:
         raise ValueError(f"mask_sample: V={V} (2..8192), k={k} (1..V)")
-    bstride = logits.stride(0) if B > 1 else max(logits.stride(0), V * T)
-    if not _rows_view(logits, V, T, bstride) or bstride < V * T:
-        logits = logits.contiguous()
-        bstride = V * T
+    (logits,), bstride = _row_blocks((logits,), V, T)
     if u is not None:
         if not isinstance(u, torch.Tensor) or u.device != logits.device or u.dtype != torch.float32 or tuple(u.shape) != (B, T, V):
             raise ValueError(f"mask_sample: u must be a float32 {(B, T, V)} tensor on {logits.device}")
@@ -584,13 +646,7 @@ def mask_sample(logits, k, u=None, temperature=1.0):
     return ids, score
 
 
-# ---- the autoregressive transformer's decode step (csrc/llama_ar.hip) ----------------
-def _f32_dev(t, name, who):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f"{who}: {name} must be a float32 tensor on a ROCm device (the HIP path has no CPU fallback)")
-    return t
-
-
+# ---- the autoregressive transformer's decode step (csrc/llama_ar.hip; the T = 1 Linear: csrc/pw_vec.hip) ----------------
 def kv_cache(B, n_heads, dk, Lmax, device):
     """one layer's (K, V) cache, two fp32 [B, H*dk, Lmax] buffers (K holds rope(k))"""
     shape = (int(B), int(n_heads) * int(dk), int(Lmax))
@@ -617,10 +673,7 @@ def kv_append(k, v, n_heads, cos, sin, pos0, kcache, vcache):
     if cos.dim() != 2 or cos.shape != sin.shape or cos.shape[1] != dk // 2 or cos.shape[0] < pos0 + T:
         raise ValueError(f"kv_append: cos and sin must be [>= {pos0 + T}, {dk // 2}], got {tuple(cos.shape)} and {tuple(sin.shape)}")
     cos, sin = cos.contiguous(), sin.contiguous()
-    bstride = k.stride(0) if B > 1 else max(k.stride(0), C * T)
-    if not (_rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
-        k, v = k.contiguous(), v.contiguous()
-        bstride = C * T
+    (k, v), bstride = _row_blocks((k, v), C, T)
     with _lib.on_device(k.device):
         _lib.check(_lib.lib().amp_kv_append(_ptr(k), _ptr(v), int(bstride), _ptr(cos), _ptr(sin), B, H, dk, T, pos0, Lmax, _ptr(kcache), _ptr(vcache),
                                             _stream(k)))
@@ -661,9 +714,7 @@ def attention_decode(q, n_heads, cos, sin, L, kcache, vcache, scale=None):
     if cos.dim() != 2 or cos.shape != sin.shape or cos.shape[1] != dk // 2 or cos.shape[0] < L:
         raise ValueError(f"attention_decode: cos and sin must be [>= {L}, {dk // 2}], got {tuple(cos.shape)} and {tuple(sin.shape)}")
     cos, sin = cos.contiguous(), sin.contiguous()
-    if (C > 1 and q.stride(1) != 1) or (B > 1 and q.stride(0) < C):
-        q = q.contiguous()
-    qbs = int(q.stride(0)) if B > 1 else C
+    q, qbs = _rows_2d(q, C)
     scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
     out = torch.empty((B, C, 1), dtype=torch.float32, device=q.device)
     with _lib.on_device(q.device):
@@ -678,13 +729,7 @@ def attention_decode(q, n_heads, cos, sin, L, kcache, vcache, scale=None):
 def pw_forward_vec(h, cout, x, gamma=None, res=None, out=None):
     """``amp_pw_forward_vec``: the Linear of the ``amp_pw`` handle ``h`` on x [B, cin, 1] (B <= 8; contiguous, or a row block of a wider
     [B, C, 1] tensor) -> [B, cout, 1]; with ``res`` (and ``gamma`` [cout]) the ``res + gamma * (Wx + b)`` epilogue"""
-    _f32_dev(x, "x", "pw_forward_vec")
-    if x.dim() != 3 or x.shape[2] != 1 or x.numel() == 0:
-        raise ValueError(f"pw_forward_vec: expected a [B, cin, 1] input, got {tuple(x.shape)}")
-    B, cin = x.shape[0], x.shape[1]
-    if (cin > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < cin):
-        x = x.contiguous()
-    xbs = int(x.stride(0)) if B > 1 else cin
+    x, B, cin, xbs = _vec_input("pw_forward_vec", x)
     if out is None:
         out = torch.empty((B, int(cout), 1), dtype=torch.float32, device=x.device)
     epi = 0 if res is None else 2
@@ -707,8 +752,7 @@ def ar_sample(logits, q, ids, n_ids, eos_id, suppress_eos, temperature=1.0, top_
     if logits.dim() != 2 or logits.numel() == 0:
         raise ValueError(f"ar_sample: logits must be [B, V] or [B, V, 1], got {tuple(logits.shape)}")
     B, V = logits.shape
-    if (V > 1 and logits.stride(1) != 1) or (B > 1 and logits.stride(0) < V):
-        logits = logits.contiguous()
+    logits, lbs = _rows_2d(logits, V)
     if tuple(q.shape) != (B, V) or q.device != logits.device:
         raise ValueError(f"ar_sample: q must be a {(B, V)} tensor on {logits.device}, got {tuple(q.shape)}")
     q = q.contiguous()
@@ -716,7 +760,7 @@ def ar_sample(logits, q, ids, n_ids, eos_id, suppress_eos, temperature=1.0, top_
             or not ids.is_contiguous():
         raise ValueError(f"ar_sample: ids must be a contiguous int64 [{B}, capacity] tensor on {logits.device}")
     with _lib.on_device(logits.device):
-        _lib.check(_lib.lib().amp_ar_sample(_ptr(logits), int(logits.stride(0)) if B > 1 else V, B, V, _ptr(q), _ptr(ids), ids.shape[1], int(n_ids),
+        _lib.check(_lib.lib().amp_ar_sample(_ptr(logits), lbs, B, V, _ptr(q), _ptr(ids), ids.shape[1], int(n_ids),
                                             int(eos_id), 1 if suppress_eos else 0, float(temperature), int(top_k), float(top_p),
                                             float(repetition_penalty), _stream(logits)))
     return ids
@@ -736,31 +780,15 @@ def mh_attention(q, k, v, n_heads, key_mask=None, scale=None):
         raise ValueError(f"mh_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
                          f"{tuple(v.shape)}")
     B, C, T = q.shape
-    H = int(n_heads)
-    if H < 1 or C % H:
-        raise ValueError(f"mh_attention: {C} channels do not divide into {H} heads")
-    dk = C // H
-    if dk != 128:
-        raise ValueError(f"mh_attention: head dimension {dk} is not covered (dk = 128)")
+    H, dk = _heads("mh_attention", C, n_heads, (128,))
     if B < 1 or T < 1:
         raise ValueError(f"mh_attention: empty input {tuple(q.shape)}")
-    if key_mask is not None:
-        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
-            raise ValueError(f"mh_attention: key_mask must be a {(B, T)} tensor on {q.device}")
-        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
-            key_mask = (key_mask != 0).to(torch.uint8)
-        key_mask = key_mask.contiguous()
+    key_mask = _key_mask_u8("mh_attention", key_mask, B, T, q.device)
     scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
     with _lib.on_device(q.device):
         if _lib.get_precision() == "f32":
-            m = None if key_mask is None else key_mask.bool()[:, None, None, :]
-            o = torch.nn.functional.scaled_dot_product_attention(*(t.reshape(B, H, dk, T).transpose(2, 3) for t in (q, k, v)), attn_mask=m,
-                                                                 scale=scale)
-            return o.transpose(2, 3).reshape(B, C, T).contiguous()
-        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
-        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            bstride = C * T
+            return _sdpa_cf(q, k, v, H, None if key_mask is None else key_mask.bool()[:, None, None, :], scale)
+        (q, k, v), bstride = _row_blocks((q, k, v), C, T)
         out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
         _lib.check(_lib.lib().amp_mh_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(key_mask), B, H, dk, T, scale, _ptr(out), _stream(q)))
     return out
@@ -796,10 +824,7 @@ def bucketize_embed_add(x, pred, control, bins, table, out=None):
                          f"{tuple(bins.shape)}, {tuple(table.shape)}")
     if any(t.device != x.device for t in (pred, bins, table)):
         raise ValueError(f"bucketize_embed_add: every tensor must be on {x.device}")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"bucketize_embed_add: out must be a contiguous float32 {tuple(x.shape)} on {x.device}")
+    out = _out_like("bucketize_embed_add", out, x)
     scaled = torch.empty_like(pred)
     with _lib.on_device(x.device):
         _lib.check(_lib.lib().amp_bucketize_embed_add(_ptr(pred), float(control), _ptr(bins), bins.shape[0], _ptr(table), table.shape[0], _ptr(x), B, D,
@@ -845,34 +870,16 @@ def _cross_attention(entry, dks, q, k, v, n_heads, key_mask, scale):
                          f"{tuple(v.shape)}")
     B, C, Tq = q.shape
     Tk = k.shape[2]
-    H = int(n_heads)
-    if H < 1 or C % H:
-        raise ValueError(f"cross_attention: {C} channels do not divide into {H} heads")
-    dk = C // H
-    if dk not in dks:
-        raise ValueError(f"cross_attention: head dimension {dk} is not covered (dk = {' / '.join(map(str, dks))})")
+    H, dk = _heads("cross_attention", C, n_heads, dks)
     if B < 1 or Tq < 1 or Tk < 1:
         raise ValueError(f"cross_attention: empty input {tuple(q.shape)}, {tuple(k.shape)}")
-    if key_mask is not None:
-        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, Tk) or key_mask.device != q.device:
-            raise ValueError(f"cross_attention: key_mask must be a {(B, Tk)} tensor on {q.device}")
-        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
-            key_mask = (key_mask != 0).to(torch.uint8)
-        key_mask = key_mask.contiguous()
+    key_mask = _key_mask_u8("cross_attention", key_mask, B, Tk, q.device)
     scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
     with _lib.on_device(q.device):
         if _lib.get_precision() == "f32":
-            m = None if key_mask is None else key_mask.bool()[:, None, None, :]
-            qq = q.reshape(B, H, dk, Tq).transpose(2, 3)
-            kk, vv = (t.reshape(B, H, dk, Tk).transpose(2, 3) for t in (k, v))
-            o = torch.nn.functional.scaled_dot_product_attention(qq, kk, vv, attn_mask=m, scale=scale)
-            return o.transpose(2, 3).reshape(B, C, Tq).contiguous()
-        qbs = q.stride(0) if B > 1 else max(q.stride(0), C * Tq)
-        if not _rows_view(q, C, Tq, qbs) or qbs < C * Tq:
-            q, qbs = q.contiguous(), C * Tq
-        kvbs = k.stride(0) if B > 1 else max(k.stride(0), C * Tk)
-        if not (_rows_view(k, C, Tk, kvbs) and _rows_view(v, C, Tk, kvbs)) or kvbs < C * Tk:
-            k, v, kvbs = k.contiguous(), v.contiguous(), C * Tk
+            return _sdpa_cf(q, k, v, H, None if key_mask is None else key_mask.bool()[:, None, None, :], scale)
+        (q,), qbs = _row_blocks((q,), C, Tq)
+        (k, v), kvbs = _row_blocks((k, v), C, Tk)
         out = torch.empty((B, C, Tq), dtype=torch.float32, device=q.device)
         _lib.check(getattr(_lib.lib(), entry)(_ptr(q), int(qbs), _ptr(k), _ptr(v), int(kvbs), _ptr(key_mask), B, H, dk, Tq, Tk, scale, _ptr(out),
                                                   _stream(q)))
@@ -922,14 +929,12 @@ class Ns2Layer:
             dconst = dconst[None]
         if dconst.dim() != 2 or dconst.shape[1] != H or dconst.shape[0] not in (1, B) or dconst.device != dev:
             raise ValueError(f"Ns2Layer: dconst must be [{H}] or [{B}, {H}] on {dev}, got {tuple(dconst.shape)}")
-        if dconst.stride(1) != 1 or (dconst.shape[0] > 1 and dconst.stride(0) < H):
-            dconst = dconst.contiguous()
-        dbs = int(dconst.stride(0)) if dconst.shape[0] > 1 else 0
+        dconst, dbs = _rows_2d(dconst, H)
+        if dconst.shape[0] == 1:
+            dbs = 0                                          # one row for every item
         if tuple(cterm.shape) != (B, 2 * H, T) or cterm.device != dev:
             raise ValueError(f"Ns2Layer: cterm must be {(B, 2 * H, T)} on {dev}, got {tuple(cterm.shape)}")
-        cbs = cterm.stride(0) if B > 1 else max(cterm.stride(0), 2 * H * T)
-        if not _rows_view(cterm, 2 * H, T, cbs) or cbs < 2 * H * T:
-            cterm, cbs = cterm.contiguous(), 2 * H * T
+        (cterm,), cbs = _row_blocks((cterm,), 2 * H, T)
         if film is not None:
             film = _lib.require_device_tensor(film, "ns2 layer FiLM")
             if tuple(film.shape) != (B, 4 * H, T) or film.device != dev:
@@ -956,10 +961,7 @@ def ns2_ode_step(x_eval, x0_pred, x_base, mean_scale, variance, h_beta, inv_sigm
     ts = [_lib.require_device_tensor(t, n) for t, n in ((x_eval, "ns2_ode_step x_eval"), (x0_pred, "ns2_ode_step x0_pred"), (x_base, "ns2_ode_step x_base"))]
     if ts[0].numel() == 0 or ts[1].shape != ts[0].shape or ts[2].shape != ts[0].shape or ts[1].device != ts[0].device or ts[2].device != ts[0].device:
         raise ValueError(f"ns2_ode_step: three non-empty tensors of one shape on one device, got {[tuple(t.shape) for t in ts]}")
-    if out is None:
-        out = torch.empty_like(ts[0])
-    elif out.shape != ts[0].shape or out.device != ts[0].device or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"ns2_ode_step: out must be a contiguous float32 {tuple(ts[0].shape)} on {ts[0].device}")
+    out = _out_like("ns2_ode_step", out, ts[0])
     with _lib.on_device(out.device):
         _lib.check(_lib.lib().amp_ns2_ode_step(_ptr(ts[0]), _ptr(ts[1]), _ptr(ts[2]), ts[0].numel(), float(mean_scale), float(variance), float(h_beta),
                                                float(inv_sigma2), 1 if midpoint_half else 0, _ptr(out), _stream(out)))
@@ -980,22 +982,12 @@ def prefix_attention(q, k, v, n_heads, prefix, key_mask=None, scale=None):
         raise ValueError(f"prefix_attention: q, k, v must be [B, H*dk, T] tensors of one shape on one device, got {tuple(q.shape)}, {tuple(k.shape)}, "
                          f"{tuple(v.shape)}")
     B, C, T = q.shape
-    H, prefix = int(n_heads), int(prefix)
-    if H < 1 or C % H:
-        raise ValueError(f"prefix_attention: {C} channels do not divide into {H} heads")
-    dk = C // H
-    if dk != 64:
-        raise ValueError(f"prefix_attention: head dimension {dk} is not covered (dk = 64)")
+    (H, dk), prefix = _heads("prefix_attention", C, n_heads, (64,)), int(prefix)
     if B < 1 or T < 1:
         raise ValueError(f"prefix_attention: empty input {tuple(q.shape)}")
     if not 0 <= prefix <= T:
         raise ValueError(f"prefix_attention: prefix={prefix} is outside [0, {T}]")
-    if key_mask is not None:
-        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, T) or key_mask.device != q.device:
-            raise ValueError(f"prefix_attention: key_mask must be a {(B, T)} tensor on {q.device}")
-        if key_mask.dtype != torch.uint8:          # the kernel reads bytes, nonzero = valid
-            key_mask = (key_mask != 0).to(torch.uint8)
-        key_mask = key_mask.contiguous()
+    key_mask = _key_mask_u8("prefix_attention", key_mask, B, T, q.device)
     scale = 1.0 / (dk ** 0.5) if scale is None else float(scale)
     with _lib.on_device(q.device):
         if _lib.get_precision() == "f32":
@@ -1003,13 +995,8 @@ def prefix_attention(q, k, v, n_heads, prefix, key_mask=None, scale=None):
             m = ((j[None, :] < prefix) | (j[None, :] <= j[:, None]))[None, None]
             if key_mask is not None:
                 m = m & key_mask.bool()[:, None, None, :]
-            o = torch.nn.functional.scaled_dot_product_attention(*(t.reshape(B, H, dk, T).transpose(2, 3) for t in (q, k, v)), attn_mask=m,
-                                                                 scale=scale)
-            return o.transpose(2, 3).reshape(B, C, T).contiguous()
-        bstride = q.stride(0) if B > 1 else max(q.stride(0), C * T)
-        if not (_rows_view(q, C, T, bstride) and _rows_view(k, C, T, bstride) and _rows_view(v, C, T, bstride)) or bstride < C * T:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            bstride = C * T
+            return _sdpa_cf(q, k, v, H, m, scale)
+        (q, k, v), bstride = _row_blocks((q, k, v), C, T)
         out = torch.empty((B, C, T), dtype=torch.float32, device=q.device)
         _lib.check(_lib.lib().amp_prefix_attention(_ptr(q), _ptr(k), _ptr(v), int(bstride), _ptr(key_mask), B, H, dk, T, prefix, scale, _ptr(out),
                                                    _stream(q)))
@@ -1020,10 +1007,7 @@ def pw_forward_vec_ln(h, cout, x, ln_gamma=None, ln_beta=None, eps=1e-5, relu=Fa
     """``amp_pw_forward_vec_ln``: ``epi(W n(x) + b)`` of the ``amp_pw`` handle ``h`` on x [B, cin, 1] (B <= 8; contiguous, or a row block of a
     wider [B, C, 1] tensor) -> [B, cout, 1].  n = LayerNorm over the cin channels with ``ln_gamma`` / ``ln_beta`` [cin] (both None: n(x) = x);
     epi = bias, bias -> ReLU (``relu``), or ``res + gamma * (.)`` (``res`` and ``gamma`` [cout]; not with ``relu``)."""
-    _f32_dev(x, "x", "pw_forward_vec_ln")
-    if x.dim() != 3 or x.shape[2] != 1 or x.numel() == 0:
-        raise ValueError(f"pw_forward_vec_ln: expected a [B, cin, 1] input, got {tuple(x.shape)}")
-    B, cin = x.shape[0], x.shape[1]
+    x, B, cin, xbs = _vec_input("pw_forward_vec_ln", x)
     if (ln_gamma is None) != (ln_beta is None):
         raise ValueError("pw_forward_vec_ln: ln_gamma and ln_beta come together")
     for t, name in ((ln_gamma, "ln_gamma"), (ln_beta, "ln_beta")):
@@ -1031,9 +1015,6 @@ def pw_forward_vec_ln(h, cout, x, ln_gamma=None, ln_beta=None, eps=1e-5, relu=Fa
             raise ValueError(f"pw_forward_vec_ln: {name} must hold {cin} contiguous values on {x.device}")
     if (res is None) != (gamma is None) or (res is not None and relu):
         raise ValueError("pw_forward_vec_ln: the residual epilogue takes res and gamma, and no relu")
-    if (cin > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < cin):
-        x = x.contiguous()
-    xbs = int(x.stride(0)) if B > 1 else cin
     if out is None:
         out = torch.empty((B, int(cout), 1), dtype=torch.float32, device=x.device)
     with _lib.on_device(x.device):
@@ -1166,14 +1147,16 @@ class Conv2d3x3:
         if stride not in (1, 2) or (up2 and stride != 1):
             raise ValueError(f"Conv2d3x3: stride={stride} up2={up2} is not covered")
         Ho, Wo = conv2d_out_size(H, W, stride, up2)
+        rbs = 0                                              # the row stride of an absent row_add / of a single item
         if row_add is not None:
             _f32_dev(row_add, "row_add", "Conv2d3x3")
             if row_add.dim() == 4 and tuple(row_add.shape[2:]) == (1, 1):
                 row_add = row_add[:, :, 0, 0]
             if tuple(row_add.shape) != (B, Cout) or row_add.device != dev:
                 raise ValueError(f"Conv2d3x3: row_add must be {(B, Cout)} on {dev}, got {tuple(row_add.shape)}")
-            if (Cout > 1 and row_add.stride(1) != 1) or (B > 1 and row_add.stride(0) < Cout):
-                row_add = row_add.contiguous()
+            row_add, rbs = _rows_2d(row_add, Cout)
+            if B == 1:
+                rbs = 0
         if residual is not None:
             residual = _lib.require_device_tensor(residual, "conv2d residual")
             if tuple(residual.shape) != (B, Cout, Ho, Wo) or residual.device != dev:
@@ -1207,7 +1190,6 @@ class Conv2d3x3:
             # stream only), so no conv leaves memory held behind it
             ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev) if nbytes else None
             mr, gamma, beta = norm if norm is not None else (None, None, None)
-            rbs = int(row_add.stride(0)) if row_add is not None and B > 1 else 0
             _lib.check(L.amp_conv2d_forward(h, _ptr(x), B, H, W, stride, int(up2), _ptr(mr), _ptr(gamma), _ptr(beta), _ptr(row_add), rbs, _ptr(residual),
                                             _ptr(y), _ptr(ws), nbytes, _stream(x)))
         return y
